@@ -10,13 +10,20 @@ under torchrun, the gradients averaged over RCCL with one flat all-reduce after
 backward (ctn_dist.FlatGradAllReduce; CTN_GRAD_SYNC=ddp for DistributedDataParallel)
 (weak scaling: per-GPU batch fixed).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (utt/s,
+ms_per_step).  --dump-outputs DIR then writes what the last timed step computed (loss,
+separated sources, clipped gradients, updated parameters) as DIR/<name>.npy; the inputs
+and the initial weights are seeded, so two builds can be compared output for output.
+Everything else the benchmark measures (per-kernel table, live roofline of the dominant
+kernel, copy and MFMA peaks, committed PMC figures, CPU baseline) runs with --full only.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment (no torchrun), bench.py
 starts the N ranks itself as child processes (spawn_ranks); under torchrun it
 is one of the ranks.
 
-Prints ONE JSON line (rank 0).  `roofline` is measured live: the dominant
+Prints ONE JSON line (rank 0).  With --full, `roofline` is measured live: the dominant
 kernel's launches inside the timed region are bracketed by hipEvents on their
 own stream (ctn_timer_*), and achieved = algorithmic bytes per launch / mean
 launch time.  `cpu_baseline` times the fp32 CPU oracle (oracle/, test
@@ -31,6 +38,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
@@ -249,6 +257,24 @@ def cpu_baseline(seconds=10.0):
                              f"{best} threads, {el1:.1f} s"}}
 
 
+DUMP_ARRAY_BYTES = 15 * 10 ** 6   # per dumped array; four arrays stay under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy in float32.  An array above
+    DUMP_ARRAY_BYTES is cut to a fixed sample of its flattened elements (sorted indices
+    drawn without replacement by a generator seeded with 0, so every run and every build
+    keeps the same elements)."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_ARRAY_BYTES // 4
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def spawn_ranks(n, cmd, port=None, env=None):
     """Start `cmd` as n ranks of one job (RANK/LOCAL_RANK/WORLD_SIZE/MASTER_*), wait for
     all of them and return the first non-zero exit code (0 when every rank succeeded).
@@ -335,9 +361,15 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="utterances per GPU (config default)")
     ap.add_argument("--seconds", type=float, default=None, help="utterance length (config default)")
     ap.add_argument("--fp32", action="store_true", help="fp32 activations (parity mode) instead of bf16")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy "
+                         "(rank 0: loss, est_source, grads, params; float32)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: per-kernel table, live "
+                         "roofline of the dominant kernel, copy and MFMA peaks, PMC figures, CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-copy-peak", action="store_true",
-                    help="skip the calibration kernels after the timed steps (copy_peak and mfma_peak: null); "
+                    help="with --full: skip the calibration kernels after the timed steps (copy_peak and mfma_peak: null); "
                          "profiling runs use it so that no calibration kernel lands in a kernel trace")
     ap.add_argument("--timer-kind", type=int, default=0,
                     help="kernel timed in the timed region (default: the dominant one of the profile pass)")
@@ -346,7 +378,7 @@ def main():
                          "hipEvents (each bracket idles the GPU a few us around the launch); 9 is "
                          "coprime with the 32 launches per step, so the samples visit every block")
     ap.add_argument("--profile-steps", type=int, default=5,
-                    help="untimed steps with every kernel family timed (the per-kernel table)")
+                    help="with --full: untimed steps with every kernel family timed (the per-kernel table)")
     ap.add_argument("--ddp", action="store_true",
                     help="the data-parallel path over RCCL even at world size 1 (process-group init, "
                          "gradient exchange)")
@@ -354,6 +386,8 @@ def main():
                     help="capture the whole step as a HIP graph after warmup and time its replays "
                          "(ctn_graph.StepGraph; one GPU, no exchange)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no outside launcher: start one rank per GPU ourselves (children, no exec); the
@@ -438,8 +472,10 @@ def main():
 
     plist = list(model.parameters())   # (model.parameters() walks every module each call)
 
+    last = {}   # the last step's separated sources, for --dump-outputs
+
     def step():
-        est = model(mix)
+        est = last["est_source"] = model(mix)
         loss = pc.cal_loss(src, est, lens)[0]
         opt.zero_grad(set_to_none=True)
         loss.backward()
@@ -456,7 +492,7 @@ def main():
     s_el = 4 if args.fp32 else 2
     # profile pass (untimed): every kernel family bracketed by hipEvents -> per-kernel table
     table = {}
-    if args.profile_steps > 0:
+    if args.full and args.profile_steps > 0:
         torch.cuda.synchronize(dev)
         L.check(lib.ctn_timer_enable_mask(sum(1 << k for k in TIMER_NAMES), args.profile_steps * 64),
                 "ctn_timer_enable_mask")
@@ -485,7 +521,8 @@ def main():
         import ctn_graph
         graph = ctn_graph.StepGraph(step, warmup=1)   # one more eager step on a side stream, then capture
     torch.cuda.synchronize(dev)
-    if graph is None:   # (a replay re-runs the captured launches: the live timer sees none of them)
+    live_timer = args.full and graph is None   # (a replay re-runs the captured launches: the timer sees none)
+    if live_timer:
         L.check(lib.ctn_timer_set_stride(args.timer_stride), "ctn_timer_set_stride")
         L.check(lib.ctn_timer_enable(args.timer_kind, args.steps * 64), "ctn_timer_enable")
     if use_ddp:
@@ -500,9 +537,10 @@ def main():
     elapsed = time.perf_counter() - t0
     tot = ctypes.c_double(0.0)
     nl = ctypes.c_int(0)
-    L.check(lib.ctn_timer_read(ctypes.byref(tot), ctypes.byref(nl)), "ctn_timer_read")
-    lib.ctn_timer_enable(0, 0)
-    lib.ctn_timer_set_stride(1)
+    if live_timer:
+        L.check(lib.ctn_timer_read(ctypes.byref(tot), ctypes.byref(nl)), "ctn_timer_read")
+        lib.ctn_timer_enable(0, 0)
+        lib.ctn_timer_set_stride(1)
     # a generation-word timeout anywhere in the run fails the bench (ctn_device_status)
     L.check(lib.ctn_device_status(ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), None, 0),
             "ctn_device_status")
@@ -516,32 +554,19 @@ def main():
         elapsed = max(float(x) for x in ts)
     final_loss = float(loss.detach())
     deferred = (ctn_ops.DEFERRED_BLOCKS - n_def0) / args.steps
-    copy_gbs, copy_how = copy_peak_gbs(dev, lib) if rank == 0 and not args.no_copy_peak else (None, None)
-    mfma_peak = mfma_peak_tflops(dev, lib) if rank == 0 and not args.no_copy_peak else None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {
+            "loss": loss, "est_source": last["est_source"],
+            "grads": torch.cat([p.grad.reshape(-1) for p in plist]),
+            "params": torch.cat([p.reshape(-1) for p in plist])})
+    calibrate = args.full and rank == 0 and not args.no_copy_peak
+    copy_gbs, copy_how = copy_peak_gbs(dev, lib) if calibrate else (None, None)
+    mfma_peak = mfma_peak_tflops(dev, lib) if calibrate else None
 
     if rank == 0:
         s = s_el
         ms = elapsed / args.steps * 1e3
         utt_s = world * M * args.steps / elapsed
-        kb = kernel_bytes(args.timer_kind, M, K, cfg, s)
-        mean_ms = tot.value / max(nl.value, 1)
-        if graph is not None and args.timer_kind in table:   # graph: the eager profile pass's timing
-            mean_ms = table[args.timer_kind]["mean_us"] * 1e-3
-            nl.value = int(round(table[args.timer_kind]["launches_per_step"] * args.steps))
-        achieved = kb / (mean_ms * 1e-3) / 1e9
-        traffic = mfma = step_pmc = None
-        pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")   # c2 FETCH_SIZE/WRITE_SIZE passes
-        if os.path.exists(pmc) and args.config == "c2":
-            with open(pmc) as f:
-                traffic = json.load(f).get(str(args.timer_kind))
-        pmc = os.path.join(ROOT, "profiles", "pmc_step.json")      # the same passes, whole step (tools/pmc_step.py)
-        if os.path.exists(pmc) and args.config == "c2" and not args.fp32:
-            with open(pmc) as f:
-                step_pmc = json.load(f).get("step_GB")
-        pmc = os.path.join(ROOT, "profiles", "pmc_mfma.json")   # tools/gpu.sh prof, MFMA pass
-        if os.path.exists(pmc):
-            with open(pmc) as f:
-                mfma = json.load(f).get(str(args.timer_kind))
         out = {
             "metric": ("utterances/sec (4s, 8kHz, 2-spk) fwd+bwd" if args.config == "c2" else
                        f"utterances/sec ({args.seconds:g}s, {rate // 1000}kHz, {C}-spk) fwd+bwd, {args.config}"),
@@ -574,33 +599,53 @@ def main():
                        # TemporalBlock backwards per step whose parameter-gradient reductions
                        # ran batched at the end of backward (ctn_tblock_reduce_grads)
                        "deferred_grad_reduce_blocks": deferred},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         "kernel": TIMER_NAMES[args.timer_kind] if not (args.timer_kind == TIMER_GEMM_BWD_A and
-                                                                        not dual_pair_a()) else
-                         "gemm_ws bwd g_n2 = gy.W2 (norm-backward epilogue)",
-                         # measured streaming ceiling on this GPU (device copy, read + write)
-                         "copy_peak": round(copy_gbs, 1) if copy_gbs else None, "copy_peak_by": copy_how,
-                         "frac_of_copy_peak": round(achieved / copy_gbs, 4) if copy_gbs else None,
-                         "launches": nl.value, "timer_stride": args.timer_stride, "mean_ms": round(mean_ms, 4), "bytes_per_launch": kb,
-                         # rocprofv3 SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 * 1024 SIMDs) of
-                         # this kernel, from the committed PMC pass (profiles/pmc_mfma.json)
-                         "mfma_util": mfma.get("mfma_util") if mfma else None,
-                         # measured matrix peak (ctn_mfma_peak) beside the dense bf16 datasheet value
-                         "mfma_peak": {"measured_tflops": mfma_peak, "datasheet_tflops": BF16_PEAK_TFLOPS},
-                         # the whole step against the same peak: SURVEY §8d compulsory bytes
-                         "step_frac": round(step_alg_bytes(M, K, T, cfg, s) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                         # every TemporalBlock kernel family, timed live in the untimed profile
-                         # pass (hipEvents on the launch stream), sorted by time per step
-                         "kernels": sorted(table.values(), key=lambda r: -r["ms_per_step"])},
-            "step_model": {"alg_bytes_GB": round(step_alg_bytes(M, K, T, cfg, s) / 1e9, 3),
-                           "alg_GBps": round(step_alg_bytes(M, K, T, cfg, s) / (ms * 1e-3) / 1e9, 1),
-                           "tflops": round(step_flops(M, K, cfg) / (ms * 1e-3) / 1e12, 1),
-                           # HBM bytes of one whole step measured by rocprofv3 (committed PMC passes)
-                           "pmc_GB": round(step_pmc, 2) if step_pmc else None},
             "final_loss": round(final_loss, 4),
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            kb = kernel_bytes(args.timer_kind, M, K, cfg, s)
+            mean_ms = tot.value / max(nl.value, 1)
+            if graph is not None and args.timer_kind in table:   # graph: the eager profile pass's timing
+                mean_ms = table[args.timer_kind]["mean_us"] * 1e-3
+                nl.value = int(round(table[args.timer_kind]["launches_per_step"] * args.steps))
+            achieved = kb / (mean_ms * 1e-3) / 1e9
+            traffic = mfma = step_pmc = None
+            pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")   # c2 FETCH_SIZE/WRITE_SIZE passes
+            if os.path.exists(pmc) and args.config == "c2":
+                with open(pmc) as f:
+                    traffic = json.load(f).get(str(args.timer_kind))
+            pmc = os.path.join(ROOT, "profiles", "pmc_step.json")      # the same passes, whole step (tools/pmc_step.py)
+            if os.path.exists(pmc) and args.config == "c2" and not args.fp32:
+                with open(pmc) as f:
+                    step_pmc = json.load(f).get("step_GB")
+            pmc = os.path.join(ROOT, "profiles", "pmc_mfma.json")   # tools/gpu.sh prof, MFMA pass
+            if os.path.exists(pmc):
+                with open(pmc) as f:
+                    mfma = json.load(f).get(str(args.timer_kind))
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                               "kernel": TIMER_NAMES[args.timer_kind] if not (args.timer_kind == TIMER_GEMM_BWD_A and
+                                                                              not dual_pair_a()) else
+                               "gemm_ws bwd g_n2 = gy.W2 (norm-backward epilogue)",
+                               # measured streaming ceiling on this GPU (device copy, read + write)
+                               "copy_peak": round(copy_gbs, 1) if copy_gbs else None, "copy_peak_by": copy_how,
+                               "frac_of_copy_peak": round(achieved / copy_gbs, 4) if copy_gbs else None,
+                               "launches": nl.value, "timer_stride": args.timer_stride, "mean_ms": round(mean_ms, 4), "bytes_per_launch": kb,
+                               # rocprofv3 SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE/8 * 1024 SIMDs) of
+                               # this kernel, from the committed PMC pass (profiles/pmc_mfma.json)
+                               "mfma_util": mfma.get("mfma_util") if mfma else None,
+                               # measured matrix peak (ctn_mfma_peak) beside the dense bf16 datasheet value
+                               "mfma_peak": {"measured_tflops": mfma_peak, "datasheet_tflops": BF16_PEAK_TFLOPS},
+                               # the whole step against the same peak: SURVEY §8d compulsory bytes
+                               "step_frac": round(step_alg_bytes(M, K, T, cfg, s) / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                               # every TemporalBlock kernel family, timed live in the untimed profile
+                               # pass (hipEvents on the launch stream), sorted by time per step
+                               "kernels": sorted(table.values(), key=lambda r: -r["ms_per_step"])}
+            out["step_model"] = {"alg_bytes_GB": round(step_alg_bytes(M, K, T, cfg, s) / 1e9, 3),
+                                 "alg_GBps": round(step_alg_bytes(M, K, T, cfg, s) / (ms * 1e-3) / 1e9, 1),
+                                 "tflops": round(step_flops(M, K, cfg) / (ms * 1e-3) / 1e12, 1),
+                                 # HBM bytes of one whole step measured by rocprofv3 (committed PMC passes)
+                                 "pmc_GB": round(step_pmc, 2) if step_pmc else None}
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_ddp:

@@ -34,11 +34,11 @@ suite)
   [ $rc -eq 0 ] || exit $rc
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || { tail $O/smoke.log; exit 1; }
   echo "smoke ok"
-  timeout -k 10 500 python bench.py > $O/bench.log 2>&1 || { tail $O/bench.log; exit 1; }
+  timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1 || { tail $O/bench.log; exit 1; }
   line $O/bench.log
-  timeout -k 10 300 python bench.py --config c4 --steps 10 --warmup 3 > $O/c4.log 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --config c4 --steps 10 --warmup 3 > $O/c4.log 2>&1 || exit 1
   line $O/c4.log
-  timeout -k 10 300 python bench.py --config c5 --steps 6 --warmup 2 > $O/c5.log 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --config c5 --steps 6 --warmup 2 > $O/c5.log 2>&1 || exit 1
   line $O/c5.log
   ;;
 tests)
@@ -47,7 +47,7 @@ tests)
   exit $rc
   ;;
 bench)
-  timeout -k 10 500 python bench.py --no-cpu-baseline "$@" > $O/bench.log 2>&1 || { tail $O/bench.log; exit 1; }
+  timeout -k 10 500 python bench.py --full --no-cpu-baseline "$@" > $O/bench.log 2>&1 || { tail $O/bench.log; exit 1; }
   line $O/bench.log
   ;;
 ab)
@@ -55,7 +55,7 @@ ab)
     for v in "$@"; do
       n=${v//[^A-Za-z0-9]/_}
       if [ "$v" = base ]; then E=(); else IFS=, read -ra E <<< "$v"; fi
-      env "${E[@]}" timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_${n}_$rep.log 2>&1 || { tail $O/bench_${n}_$rep.log; exit 1; }
+      env "${E[@]}" timeout -k 10 300 python bench.py --full --no-cpu-baseline ${BENCH_ARGS:-} > $O/bench_${n}_$rep.log 2>&1 || { tail $O/bench_${n}_$rep.log; exit 1; }
       echo "$v: $(line $O/bench_${n}_$rep.log)"
     done
   done
@@ -63,9 +63,9 @@ ab)
 prof)
   # the live-timer line and the kernel statistics from one profiled run (the profiler's
   # overhead is the ratio of this line's ms/step to an unprofiled line's)
-  timeout -k 10 300 python bench.py --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_unprof.log 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_unprof.log 2>&1 || exit 1
   echo "unprofiled: $(line $O/bench_unprof.log)"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof -o run --output-format csv -- python3 bench.py --no-cpu-baseline --no-copy-peak --steps 10 --warmup 3 --profile-steps 0 > $O/prof.log 2>&1 || { tail $O/prof.log; exit 1; }
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof -o run --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-copy-peak --steps 10 --warmup 3 --profile-steps 0 > $O/prof.log 2>&1 || { tail $O/prof.log; exit 1; }
   echo "profiled:   $(line $O/prof.log)"
   python3 tools/prof_summary.py $(ls $O/prof/*kernel_stats.csv | head -1) 13 16 | tee $O/kernel_summary.txt
   i=0
@@ -77,14 +77,14 @@ prof)
   python3 tools/pmc_step.py $O/pmc $(ls $O/prof/*kernel_trace.csv | head -1) 52.95 $O/pmc_step.json
   timeout -s KILL 180 rocprofv3 --pmc SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --kernel-trace --output-format csv -d $ROOT/$O/pmc/mfma -o run -- python3 bench.py --no-cpu-baseline --no-copy-peak --steps 3 --warmup 1 --profile-steps 0 > $O/pmc_mfma.log 2>&1 || exit 1
   python3 tools/pmc_mfma.py $O/pmc/mfma $O/pmc_mfma.json | tee $O/mfma_util.txt
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$O/profc4 -o run --output-format csv -- python3 bench.py --config c4 --no-copy-peak --steps 4 --warmup 2 --profile-steps 0 > $O/profc4.log 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$O/profc4 -o run --output-format csv -- python3 bench.py --full --config c4 --no-copy-peak --steps 4 --warmup 2 --profile-steps 0 > $O/profc4.log 2>&1 || exit 1
   python3 tools/prof_summary.py $(ls $O/profc4/*kernel_stats.csv | head -1) 6 12 | tee $O/c4_kernel_summary.txt
   ;;
 cfgprof)
   c=$1
-  timeout -k 10 300 python bench.py --config $c --steps 8 --warmup 3 > $O/${c}_bench.log 2>&1 || exit 1
+  timeout -k 10 300 python bench.py --full --config $c --steps 8 --warmup 3 > $O/${c}_bench.log 2>&1 || exit 1
   echo "$c: $(line $O/${c}_bench.log)"
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof$c -o run --output-format csv -- python3 bench.py --config $c --no-copy-peak --steps 4 --warmup 2 --profile-steps 0 > $O/prof$c.log 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $ROOT/$O/prof$c -o run --output-format csv -- python3 bench.py --full --config $c --no-copy-peak --steps 4 --warmup 2 --profile-steps 0 > $O/prof$c.log 2>&1 || exit 1
   python3 tools/prof_summary.py $(ls $O/prof$c/*kernel_stats.csv | head -1) 6 16 | tee $O/${c}_kernel_summary.txt
   ;;
 mb)
