@@ -1021,6 +1021,8 @@ static hipError_t ws_launch_shape(const GemmRows& p, hipStream_t s) {
     else if (ws_slices(p) == 3) {
       if constexpr (OPK == OP_PLAIN && EPI == EPI_STORE)
         hipLaunchKernelGGL((gemm_ws_kernel<OPK, NK, EPI, 2, 8, 16, 2, 3>), grid, dim3(1024), 0, s, p);
+      else   // no three-slice instantiation of this form (gemm_ws_eligible admits none): nothing would run
+        return hipErrorInvalidValue;
     } else if (ws_slices(p) == 2)
       hipLaunchKernelGGL((gemm_ws_kernel<OPK, NK, EPI, 2, 8, 8, 2, 2>), grid, dim3(512), 0, s, p);
     else

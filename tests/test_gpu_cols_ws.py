@@ -3,8 +3,9 @@ only, plain bf16 operands, transposed partials; opt-in, CTN_COLS_WS=1) that can 
 the first 1x1 conv's weight gradient dW1 = gh1^T . x in the block backward, checked through the public 1x1
 conv layer (ctn_conv1x1_backward: dW = gy^T . x, the same GemmCols shape C=256 -> 512):
 against an fp32 matmul of the same bf16 operands, against the tiled column kernel
-(CTN_COLS_WS=0), and run to run bitwise.  Padded frame rows contribute nothing.  GPU
-only."""
+(CTN_COLS_WS=0), and run to run bitwise; and, with integer operands whose sums are exact
+in fp32, for EQUALITY with an fp64 matmul and with the tiled kernel at the kernel's own
+tile and range edges.  Padded frame rows contribute nothing.  GPU only."""
 import os
 import sys
 
@@ -50,3 +51,34 @@ def test_cols_ws_matches_fp32_and_tiled_kernel(M, K, monkeypatch):
     c = _dw(x, gy, fr, 512)
     e2 = float((a - c).norm() / c.norm())
     assert e2 < 1e-5, e2
+
+
+# The kernel's own edges: 32-row tiles over min(tiles, 64) row ranges for P = 512 (four
+# 128-channel slices of a 256-workgroup grid).  K = 100: Kp = 128, 4 M tiles: M = 1 -> 4
+# ranges of one tile, 15 -> 60, 16 -> exactly 64, 17 -> 68 tiles (1-2 per range), 33 -> 132
+# (2-3 per range); (3, 300): Kp = 384, 36 ranges, a padding band inside the grid.
+@pytest.mark.parametrize("M,K", [(1, 100), (15, 100), (16, 100), (17, 100), (33, 100), (3, 300)])
+def test_cols_ws_integer_exact(M, K, monkeypatch):
+    """x and gy from {-1, 0, 1}: every product and partial sum is an exact fp32 integer, so
+    neither the row ranges nor the slab reduction may change a bit: dW EQUALS the fp64
+    matmul and the tiled kernel's result."""
+    import ctn_ops as ops
+    fr = ops.Frames.of(M, K)
+    g = torch.Generator().manual_seed(M * 7 + K)
+    x = torch.randint(-1, 2, (fr.rows, 256), generator=g, dtype=torch.int8)
+    gy = torch.randint(-1, 2, (fr.rows, 512), generator=g, dtype=torch.int8)
+    pad = torch.arange(fr.rows) % fr.Kp >= K                   # padded frames are zero rows
+    x[pad] = 0
+    gy[pad] = 0
+    x, gy = x.to(DEV), gy.to(DEV)
+    ref = gy.double().t() @ x.double()                         # [512][256], |ref| < 2^24
+    xs, gys = x.to(torch.bfloat16), gy.to(torch.bfloat16)
+    monkeypatch.setenv("CTN_COLS_WS", "1")
+    a = _dw(xs, gys, fr, 512)
+    b = _dw(xs, gys, fr, 512)
+    assert torch.equal(a, b), "run-to-run"
+    bad = a.double() != ref
+    assert not bool(bad.any()), (int(bad.sum()), bad.nonzero()[:4].tolist())
+    monkeypatch.setenv("CTN_COLS_WS", "0")
+    c = _dw(xs, gys, fr, 512)
+    assert torch.equal(a, c), "wave-specialised vs tiled kernel"
