@@ -45,68 +45,29 @@ clean:
 
 # bound-finding microbenchmarks (not part of the library): build/ws_bench_<bits>
 MB_EXPS := 0 1 2 3 4 8 12
-microbench: $(patsubst %,build/ws_bench_%,$(MB_EXPS))
+microbench: $(patsubst %,build/ws_bench_%,$(MB_EXPS)) build/ws_bench_stamp
 build/ws_bench_%: tools/microbench/ws_bench.hip $(PKG)/csrc/ctn_gemm_ws.hip $(HDR)
 	@mkdir -p build
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_WS_EXP=$* $< -o $@
+# phase-stamp build: build/ws_bench_stamp
+build/ws_bench_stamp: tools/microbench/ws_bench.hip $(PKG)/csrc/ctn_gemm_ws.hip $(HDR)
+	@mkdir -p build
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_WS_STAMP=1 $< -o $@
 
 .PHONY: microbench
 
-# dual-GEMM bound-finding microbenchmarks: build/dual_bench_<bits>
-DU_EXPS := 0 12 13 14 28 76 92 94 222
-dualbench: $(patsubst %,build/dual_bench_%,$(DU_EXPS))
-build/dual_bench_%: tools/microbench/dual_bench.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DU_EXP=$* $< -o $@
-
-.PHONY: dualbench
-
 # wave-specialised pair-A dual GEMM vs gemm_dual_kernel: build/dual_ws_bench_<bits>
 DV_EXPS := 0 1 2 4 8 32 34 64 96
-dualws: $(patsubst %,build/dual_ws_bench_%,$(DV_EXPS))
+dualws: $(patsubst %,build/dual_ws_bench_%,$(DV_EXPS)) build/dual_ws_bench_stamp
 build/dual_ws_bench_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
 	@mkdir -p build
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_EXP=$* $< -o $@
+# phase-stamp build: build/dual_ws_bench_stamp
+build/dual_ws_bench_stamp: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
+	@mkdir -p build
+	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_STAMP=1 $< -o $@
 
 .PHONY: dualws
-
-# diagnostic builds of the wave-specialised kernel: build/dual_ws_dbg_<bits>
-DV_DBGS := 16 8
-dualwsdbg: $(patsubst %,build/dual_ws_dbg_%,$(DV_DBGS))
-build/dual_ws_dbg_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_DBG=$* $< -o $@
-
-# slot layout x ring depth x column split: build/dual_ws_var_<rawb>_<nsl>_<cj>_<exp>
-# (CTN_DV_RAWB, CTN_DV_NSL, CTN_DV_CJ, CTN_DV_EXP)
-DV_VARS := 0_4_4_0 0_4_2_0 0_4_1_0 1_6_4_0 1_6_2_0 1_6_1_0 0_4_2_2 1_6_2_2 0_4_2_8 1_6_2_8 0_4_2_18 1_6_2_18 1_6_2_10 0_4_2_10
-dualwsvar: $(patsubst %,build/dual_ws_var_%,$(DV_VARS))
-build/dual_ws_var_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_RAWB=$(word 1,$(subst _, ,$*)) \
-	  -DCTN_DV_NSL=$(word 2,$(subst _, ,$*)) -DCTN_DV_CJ=$(word 3,$(subst _, ,$*)) -DCTN_DV_EXP=$(word 4,$(subst _, ,$*)) $< -o $@
-
-.PHONY: dualwsvar
-
-# N-image / column-wave variants: build/dual_ws_nv_<nimg>_<nc>_<cj>_<exp>_<la>
-# (CTN_DV_NIMG, CTN_DV_NC, CTN_DV_CJ = CTN_DV_CJN, CTN_DV_EXP, CTN_DV_LA)
-NV_VARS := 0_8_1_0_1 0_4_2_0_1 0_4_2_0_2 0_4_4_0_1 1_4_2_0_2
-dualwsnv: $(patsubst %,build/dual_ws_nv_%,$(NV_VARS))
-build/dual_ws_nv_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_NIMG=$(word 1,$(subst _, ,$*)) \
-	  -DCTN_DV_NC=$(word 2,$(subst _, ,$*)) -DCTN_DV_CJ=$(word 3,$(subst _, ,$*)) -DCTN_DV_CJN=$(word 3,$(subst _, ,$*)) \
-	  -DCTN_DV_EXP=$(word 4,$(subst _, ,$*)) -DCTN_DV_LA=$(word 5,$(subst _, ,$*)) $< -o $@
-
-.PHONY: dualwsnv
-
-# column waves' tiles per iteration: build/dual_ws_c2_<0|1>
-dualwsc2: build/dual_ws_c2_0 build/dual_ws_c2_1
-build/dual_ws_c2_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_C2=$* $< -o $@
-.PHONY: dualwsc2
-.PHONY: dualwsdbg
 
 # library variants for A/B runs (tools/gpu_variants.sh, loaded through CTN_HIP_LIB):
 #   make varlib VAR=<tag> VDEV="<device flags>" VDEF="<-D...>" -> build/var/lib<tag>.so
@@ -121,58 +82,3 @@ build/var/lib$(VAR).so: $(VOBJ)
 	$(HIPCC) -shared -fPIC --offload-arch=$(ARCH) -o $@ $(VOBJ)
 varlib: build/var/lib$(VAR).so
 .PHONY: varlib
-
-# round 6: dual GEMM variants by -D flags: build/dv6_<name> from DV6_<name> (tools/gpu.sh mb)
-DV6_base :=
-DV6_p0 := -DCTN_DV_PRIO=0
-DV6_prow := -DCTN_DV_PRIO=1
-DV6_pcol := -DCTN_DV_PRIO=4
-DV6_pmem := -DCTN_DV_PRIO=16
-DV6_pmem2 := -DCTN_DV_PRIO=32
-DV6_partnt0 := -DCTN_PART_NT=0
-DV6_clnc0 := -DCTN_DV_CLNC=0
-DV6_p17 := -DCTN_DV_PRIO=17
-DV6_p18 := -DCTN_DV_PRIO=18
-DV6_p33 := -DCTN_DV_PRIO=33
-DV6_p48 := -DCTN_DV_PRIO=48
-DV6_p20 := -DCTN_DV_PRIO=20
-DV6_p34 := -DCTN_DV_PRIO=34
-DV6_p49 := -DCTN_DV_PRIO=49
-DV6_p50 := -DCTN_DV_PRIO=50
-DV6_p37 := -DCTN_DV_PRIO=37
-DV6_la2 := -DCTN_DV_LA=2
-DV6_pf4 := -DCTN_DV_PF=4
-DV6_pf3 := -DCTN_DV_PF=3
-DV6_nc4 := -DCTN_DV_NC=4 -DCTN_DV_CJ=2
-DV6_la0 := -DCTN_DV_LA=0
-DV6_e1 := -DCTN_DV_EXP=1
-DV6_e2 := -DCTN_DV_EXP=2
-DV6_e64 := -DCTN_DV_EXP=64
-DV6_e32 := -DCTN_DV_EXP=32
-DV6_e34 := -DCTN_DV_EXP=34
-DV6_e96 := -DCTN_DV_EXP=96
-DV6_e4 := -DCTN_DV_EXP=4
-DV6_e8 := -DCTN_DV_EXP=8
-DV6_st := -DCTN_DV_STAMP=1
-DV6_st2 := -DCTN_DV_STAMP=1 -DCTN_DV_EXP=2
-DV6_st64 := -DCTN_DV_STAMP=1 -DCTN_DV_EXP=64
-DV6_st0 := -DCTN_DV_STAMP=1 -DCTN_DV_PRIO=0
-DV6_NAMES := st st2 st64 st0 e1 e2 e64 e32 e34 e96 e4 e8 la2 pf4 pf3 nc4 la0 base p0 prow pcol pmem pmem2 partnt0 clnc0 p17 p18 p33 p48 p20 p34 p49 p50 p37
-dv6: $(patsubst %,build/dv6_%,$(DV6_NAMES))
-build/dv6_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) $(DV6_$*) $< -o $@
-.PHONY: dv6
-
-# round 6: WS GEMM variants by -D flags: build/ws6_<name> from WS6_<name>
-WS6_base :=
-WS6_pp := -DCTN_WS_PP=1
-WS6_la1 := -DCTN_WS_LA16=1
-WS6_la2 := -DCTN_WS_LA16=2
-WS6_pr := -DCTN_WS_PRIO=1
-WS6_NAMES := base pp la1 la2 pr
-ws6: $(patsubst %,build/ws6_%,$(WS6_NAMES))
-build/ws6_%: tools/microbench/ws_bench.hip $(PKG)/csrc/ctn_gemm_ws.hip $(HDR)
-	@mkdir -p build
-	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) $(WS6_$*) $< -o $@
-.PHONY: ws6

@@ -955,7 +955,7 @@ static int tb_backward(const ctn_tblock_desc* d, const ctn_tblock_params* p, con
   else
     da.sm1_out = L.sums1;   // cLN: per-row norm-1 backward means final in the depthwise kernel
   // cLN: the wave-item depthwise backward folds the dual's per-row partials itself (at most
-  // 4 per row: ctn_dual_ws.hip CTN_DV_CLNC) instead of a finalize launch
+  // 4 per row: dual_ws_cln_parts_per_slice) instead of a finalize launch
   if (!fold) {
     if (dualA && L.partsA <= 4 && dw_wave_eligible(dt, da))
       da.f_sm2 = gemm_dual_stat_fold(duA, L.slabA, cnt, 0.f, 1, nullptr);

@@ -58,29 +58,14 @@ template <> struct Vec8<bf16raw> {
 // memcpy's, so arrays of them stay in registers (a struct copy can keep an
 // alloca alive in scratch or LDS).
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-// CTN_NT bits (experiment switch): 1 = 16-byte loads, 2 = 16-byte stores carry the
-// nontemporal hint
-#ifndef CTN_NT
-#define CTN_NT 0
-#endif
-CTN_DEV v4u ldg16(const void* p) {
-  if constexpr (CTN_NT & 1) return __builtin_nontemporal_load(reinterpret_cast<const v4u*>(p));
-  else return *reinterpret_cast<const v4u*>(p);
-}
-CTN_DEV void stg16(void* p, v4u v) {
-  if constexpr (CTN_NT & 2) __builtin_nontemporal_store(v, reinterpret_cast<v4u*>(p));
-  else *reinterpret_cast<v4u*>(p) = v;
-}
-// CTN_PART_NT: the fp32 split-K partial sums of the dual and column GEMMs (read back only
-// by the reductions at the end of the backward pass) are stored with the nontemporal
-// hint, so they do not evict the activations the next kernels read from the Infinity
-// Cache (dw_bwd after the dual 85 -> 77 us, the dual itself +2.4, the column GEMM -1.5;
-// DESIGN.md §15).  1: one dword per lane and row; 2 (experiment, slower): 16-byte
-// stores after a quad transpose of the accumulators; 0: plain stores.
-#ifndef CTN_PART_NT
-#define CTN_PART_NT 1
-#endif
-template <bool NT = (CTN_PART_NT != 0)> CTN_DEV void st_part(float* p, float v) {
+CTN_DEV v4u ldg16(const void* p) { return *reinterpret_cast<const v4u*>(p); }
+CTN_DEV void stg16(void* p, v4u v) { *reinterpret_cast<v4u*>(p) = v; }
+// The fp32 split-K partial sums of the dual and column GEMMs (read back only by the
+// reductions at the end of the backward pass) are stored with the nontemporal hint (NT,
+// one dword per lane and row), so they do not evict the activations the next kernels read
+// from the Infinity Cache (dw_bwd after the dual 85 -> 77 us, the dual itself +2.4, the
+// column GEMM -1.5).
+template <bool NT> CTN_DEV void st_part(float* p, float v) {
   if constexpr (NT) __builtin_nontemporal_store(v, p);
   else *p = v;
 }
@@ -119,17 +104,13 @@ CTN_DEV void lds_barrier() {
   asm volatile("" ::: "memory");
 }
 
-// Generation words in LDS (ring hand-offs between waves of one workgroup, no barrier):
-// a wave publishes `gen` in its word of a slot after its own LDS operations on the slot
-// completed (flag_signal), and a consumer polls the N words of a slot until all reach
-// `gen` (flag_wait; wave-uniform by readfirstlane).  The poll is bounded (CTN_SPIN_LIMIT
-// polls, ~0.2 s) so that a protocol error cannot leave a wave spinning forever; when the
-// bound runs out the wave sets CTN_DEVERR_SPIN in the device error word `err` (one vector
+// Generation words in LDS (ring hand-offs between waves of one workgroup, no barrier;
+// ctn_dual_ws.hip's dv_wait / dv_signal).  The poll is bounded (CTN_SPIN_LIMIT polls,
+// ~0.2 s) so that a protocol error cannot leave a wave spinning forever; when the bound
+// runs out the wave sets CTN_DEVERR_SPIN in the device error word `err` (one vector
 // atomic by lane 0) and goes on, and the host reports the launch as failed
 // (ctn_device_status, ctn_tblock_reduce_grads: CTN_ERR_HIP) instead of returning its
 // wrong results silently.
-// Volatile accesses keep their address space only through an LDS-typed pointer (a
-// generic one becomes a FLAT access, whose wait drains every outstanding global load).
 #ifndef CTN_SPIN_LIMIT
 #define CTN_SPIN_LIMIT (1u << 22)
 #endif
@@ -138,30 +119,6 @@ CTN_DEV void lds_barrier() {
 #endif
 CTN_DEV void spin_timeout(uint32_t* err) {
   if (err && (threadIdx.x & 63) == 0) atomicOr(err, CTN_DEVERR_SPIN);
-}
-typedef __attribute__((address_space(3))) volatile v4u flag_v4u;
-typedef __attribute__((address_space(3))) volatile uint32_t flag_u32;
-template <int N> CTN_DEV void flag_wait(const uint32_t* f, uint32_t gen, uint32_t* err) {
-  static_assert(N % 4 == 0, "generation words per slot: whole 16-byte reads");
-  const flag_v4u* fl = (const flag_v4u*)(f);
-  uint32_t it = 0;
-  for (; it < CTN_SPIN_LIMIT; ++it) {
-    uint32_t mn = 0xffffffffu;
-#pragma unroll
-    for (int i = 0; i < N / 4; ++i) {
-      const v4u a = fl[i];
-      mn = min(mn, min(min(a[0], a[1]), min(a[2], a[3])));
-    }
-    if (__builtin_amdgcn_readfirstlane(mn) >= gen) break;
-    __builtin_amdgcn_s_sleep(1);
-  }
-  if (it == CTN_SPIN_LIMIT) spin_timeout(err);
-  asm volatile("" ::: "memory");
-}
-CTN_DEV void flag_signal(uint32_t* f, uint32_t gen) {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  *(flag_u32*)(f) = gen;
-  asm volatile("" ::: "memory");
 }
 
 // Buffer resources and LDS-DMA (the dual GEMM and the plain column GEMM)
@@ -178,23 +135,16 @@ CTN_DEV rsrc_t du_rsrc(const void* p, long bytes) {
 CTN_DEV uint32_t du_ldsaddr(const char* p) {
   return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) const char*)p);
 }
-// CTN_DMA_TAIL: wait states after the LDS-DMA issue (diagnostic builds)
-#ifndef CTN_DMA_TAIL
-#define CTN_DMA_TAIL ""
-#endif
-#ifndef CTN_DMA_HEAD
-#define CTN_DMA_HEAD "s_nop 0\n\t"
-#endif
 CTN_DEV void du_dma16(rsrc_t r, const char* lds, uint32_t voff, int soff) {
   uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\t" CTN_DMA_HEAD "buffer_load_dwordx4 %1, %2, %4 offen lds\n\t" CTN_DMA_TAIL "s_mov_b32 m0, %0"
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
                : "v"(voff), "s"(r), "s"(du_ldsaddr(lds)), "s"(soff)
                : "memory");
 }
 CTN_DEV void du_dma4(rsrc_t r, const char* lds, uint32_t voff, int soff) {
   uint32_t keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\t" CTN_DMA_HEAD "buffer_load_dword %1, %2, %4 offen lds\n\t" CTN_DMA_TAIL "s_mov_b32 m0, %0"
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tbuffer_load_dword %1, %2, %4 offen lds\n\ts_mov_b32 m0, %0"
                : "=&s"(keep)
                : "v"(voff), "s"(r), "s"(du_ldsaddr(lds)), "s"(soff)
                : "memory");
@@ -341,26 +291,6 @@ template <typename V> CTN_DEV V wave_sum_group(V v, int width) {
 template <int CTRL, int ROW_MASK> CTN_DEV float dpp_f(float x) {
   return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, x), CTRL, ROW_MASK, 0xF, false));
 }
-// 4x4 transpose within each quad of lanes (DPP quad_perm, no LDS): on entry lane t = lane & 3
-// holds v[e] = M[e][t], on exit v[c] = M[t][c].  Every lane of a quad must be active.
-CTN_DEV void quad_transpose4(float v[4]) {
-  const int t = (int)(threadIdx.x & 3);
-#pragma unroll
-  for (int e = 0; e < 4; e += 2) {   // partner t ^ 1 (quad_perm [1,0,3,2])
-    const float r = dpp_f<0xB1, 0xF>((t & 1) ? v[e] : v[e + 1]);
-    if (t & 1) v[e] = r;
-    else v[e + 1] = r;
-  }
-#pragma unroll
-  for (int e = 0; e < 2; ++e) {      // partner t ^ 2 (quad_perm [2,3,0,1])
-    const float r = dpp_f<0x4E, 0xF>((t & 2) ? v[e] : v[e + 2]);
-    if (t & 2) v[e] = r;
-    else v[e + 2] = r;
-  }
-}
-CTN_DEV v4u f4bits(const float v[4]) {
-  return v4u{__float_as_uint(v[0]), __float_as_uint(v[1]), __float_as_uint(v[2]), __float_as_uint(v[3])};
-}
 CTN_DEV float wave_sum_dpp(float v) {
   v += dpp_f<0xB1, 0xF>(v);    // quad_perm [1,0,3,2]
   v += dpp_f<0x4E, 0xF>(v);    // quad_perm [2,3,0,1]
@@ -404,29 +334,13 @@ CTN_DEV double wave_sum_dpp_d(double v) {
 }
 
 // float2 (packed fp32: v_pk_add/mul/fma_f32 on gfx950) helpers
-// IEEE maximum/minimum (NaN-propagating): one v_maximum3/v_minimum3_f32 per element on
-// gfx950, where maxnum/minnum in IEEE mode also quiet each non-arithmetic input first
-// (two more v_max_f32 per element)
-// 0 (default): maxnum/minnum as before.  1 measured neutral (fwd1 51.5 -> 51.2 us); in
-// round 2 it moved the dual GEMM's code placement into the epilogue/LDS-DMA
-// reproducibility problem of DESIGN.md §10 (round 3: reproducible, profiles/r03/race)
-#ifndef CTN_IEEE_MAX
-#define CTN_IEEE_MAX 0
-#endif
-#if CTN_IEEE_MAX
-CTN_DEV f32x2_t pmax(f32x2_t a, f32x2_t b) { return __builtin_elementwise_maximum(a, b); }
-CTN_DEV f32x2_t pmin(f32x2_t a, f32x2_t b) { return __builtin_elementwise_minimum(a, b); }
-#else
-CTN_DEV f32x2_t pmax(f32x2_t a, f32x2_t b) { return __builtin_elementwise_max(a, b); }
-CTN_DEV f32x2_t pmin(f32x2_t a, f32x2_t b) { return __builtin_elementwise_min(a, b); }
-#endif
 CTN_DEV f32x2_t pfma(f32x2_t a, f32x2_t b, f32x2_t c) { return __builtin_elementwise_fma(a, b, c); }
 // PReLU with one shared alpha: max(x, a*x) when a <= 1, min(x, a*x) when a > 1 (both
 // exact: the branch is chosen once per kernel, LE1 = (alpha <= 1)).  One v_max_f32 /
 // v_min_f32 per element: fmaxf / fminf in IEEE mode first copy every operand not known to
 // be canonical through another v_max_f32 (NaN quieting), a third of the PReLU's
 // instructions; the operands here are finite activations, for which the results agree bit
-// for bit.  (CTN_IEEE_MAX=1 keeps the round-2 builtin forms for A/B.)
+// for bit.
 template <bool LE1> CTN_DEV float prelu_nq(float x, float a) {
   const float ax = x * a;
   float r;
@@ -435,12 +349,7 @@ template <bool LE1> CTN_DEV float prelu_nq(float x, float a) {
   return r;
 }
 template <bool LE1> CTN_DEV f32x2_t prelu2(f32x2_t x, float a) {
-#if CTN_IEEE_MAX
-  const f32x2_t ax = x * a;
-  return LE1 ? pmax(x, ax) : pmin(x, ax);
-#else
   return f32x2_t{prelu_nq<LE1>(x.x, a), prelu_nq<LE1>(x.y, a)};
-#endif
 }
 
 // Block-wide sum of NV doubles; result valid in thread 0.  `red` must hold

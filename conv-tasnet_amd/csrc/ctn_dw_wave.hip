@@ -58,24 +58,11 @@ CTN_DEV void unpack8(const v4u& v, float f[8]) { unpack_bf16x8(v, f); }
 // with 16 wait states after the store, or with a global store: tools/exp/dw_debug.py,
 // DESIGN.md §15).  The compiler inserts no wait state for it: its hazard model treats a
 // >64-bit MUBUF store with a register soffset as safe.
-// CTN_DW_NT bits: the nontemporal hint on the forward's d rows (1) and on the backward's
-// dL/da1 rows (2).  Both on: the rows stream past the Infinity Cache instead of evicting
-// what the next kernels read from it (dw_fwd 44.6 -> 38.4 us, the H -> B GEMM after it
-// 47.5 -> 42.5, dw_bwd 82.5 -> 80); the hint on the producers of h1, dL/dn2
-// or dL/dh1 slows their consumers instead.
-#ifndef CTN_DW_NT
-#define CTN_DW_NT 3
-#endif
-// CTN_DW_NTL bits: the nontemporal hint on dw_bwd's d and dL/dn2 loads (1: their last use;
-// dw_bwd -2.8 us, gx after it -1.7, the next dual +2.4), on dw_fwd's h1 loads (2: dw_fwd
-// +6.4, off)
-// 1: dw_bwd's per-channel constants half-major in LDS (conflict-free reads); 0: lane-major
-#ifndef CTN_DW_CSTH
-#define CTN_DW_CSTH 1
-#endif
-#ifndef CTN_DW_NTL
-#define CTN_DW_NTL 1
-#endif
+// NT: the store carries the nontemporal hint.  On for the forward's d rows and the
+// backward's dL/da1 rows: they stream past the Infinity Cache instead of evicting what the
+// next kernels read from it (dw_fwd 44.6 -> 38.4 us, the H -> B GEMM after it 47.5 -> 42.5,
+// dw_bwd 82.5 -> 80); the hint on the producers of h1, dL/dn2 or dL/dh1
+// slows their consumers instead.
 template <bool NT = false>
 CTN_DEV void row_store(void* base, v4u v, int row) {
   stg16h<NT>(reinterpret_cast<char*>(base) + (size_t)row * 1024 + (threadIdx.x & 63) * 16u, v);
@@ -128,7 +115,7 @@ __global__ __launch_bounds__(256, 4) void dw_fwd_wave_kernel(DwArgs a) {
   const int jK = steps_below(K, it.rho, dil);
   auto row_at = [&](int s) { return it.base + ((unsigned)s < (unsigned)jK ? it.rho + s * dil : 0); };
   auto ld = [&](int row) {
-    return __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rH, vo, row * (H * 2), (CTN_DW_NTL & 2) ? 2 : 0));
+    return __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(rH, vo, row * (H * 2), 0));
   };
 
   // cLN statistics of the newest row, in batches of CB steps (as dw_bwd_wave_kernel)
@@ -209,7 +196,7 @@ __global__ __launch_bounds__(256, 4) void dw_fwd_wave_kernel(DwArgs a) {
       for (int e = 0; e < 8; ++e) o[e] = 0.f;
     }
     if (!EDGE || k < Kp)
-      row_store<(CTN_DW_NT & 1) != 0>(a.d_out, pack_bf16x8v(o), it.base + k);
+      row_store<true>(a.d_out, pack_bf16x8v(o), it.base + k);
     if constexpr (NK == NORM_GLN) {
       ts += s;
       tss += ss;
@@ -324,7 +311,7 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
   // of each group on one 16-byte slot: a 2-way conflict on every read of the walk).
   __shared__ __attribute__((aligned(16))) float cst[P + 3][H];   // w[0..P-1], gamma1, beta1, gamma2
   for (int i = threadIdx.x; i < H; i += 256) {
-    const int c = CTN_DW_CSTH ? ((i >> 2) & 1) * (H / 2) + (i >> 3) * 4 + (i & 3) : i;   // i = 8 lane + 4 hf + k
+    const int c = ((i >> 2) & 1) * (H / 2) + (i >> 3) * 4 + (i & 3);   // i = 8 lane + 4 hf + k
 #pragma unroll
     for (int t = 0; t < P; ++t) cst[t][c] = a.wd[i * P + t];
     cst[P][c] = a.gamma1[i];
@@ -337,12 +324,12 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
   // (the lane's LDS base is re-derived opaquely once per use site, cbase(), so the loads are
   // not hoisted out of the walk; the row / half offsets fold into the instructions' offsets)
   auto cbase = [&]() __attribute__((always_inline)) {
-    uint32_t b = lane * (CTN_DW_CSTH ? 16u : 32u);
+    uint32_t b = lane * 16u;
     asm volatile("" : "+v"(b));
     return b;
   };
   auto cvec4 = [&](uint32_t b, int r, int hf) __attribute__((always_inline)) {   // channels 8 lane + 4 hf ..
-    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(&cst[0][0]) + b + (r * H * 4 + hf * (CTN_DW_CSTH ? H * 2 : 16)));
+    return *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(&cst[0][0]) + b + (r * H * 4 + hf * (H * 2)));
   };
   auto f4 = [](const float4& v, int i) { return i == 0 ? v.x : i == 1 ? v.y : i == 2 ? v.z : v.w; };
   float cgam[8], cbet[8], cgam2[8], cbet2[8], cwd[P][8];
@@ -361,9 +348,10 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
   // compiler sink one step's accumulations into the next step's blocks)
   auto row_at = [&](int s) { return it.base + ((unsigned)s < (unsigned)jK ? it.rho + s * dil : 0); };
   auto ld = [&](rsrc_t r, int row) { return __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, vo, row * (H * 2), 0)); };
-  // d and dL/dn2 are read here for the last time (CTN_DW_NTL bit 0: with the nontemporal hint)
+  // d and dL/dn2 are read here for the last time, with the nontemporal hint (dw_bwd -2.8 us,
+  // gx after it -1.7, the next dual +2.4; on dw_fwd's h1 loads it cost +6.4)
   auto ld_last = [&](rsrc_t r, int row) {
-    return __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, vo, row * (H * 2), (CTN_DW_NTL & 1) ? 2 : 0));
+    return __builtin_bit_cast(v4u, __builtin_amdgcn_raw_buffer_load_b128(r, vo, row * (H * 2), 2));
   };
   auto load_row = [&](int j, BwdRow& r) __attribute__((always_inline)) {
     const int rg = row_at(j + GT);
@@ -559,7 +547,7 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
       for (int e = 0; e < 8; ++e) ga1[e] = 0.f;
     }
     if (!EDGE || k < Kp)
-      row_store<(CTN_DW_NT & 2) != 0>(a.ga1_out, pack_bf16x8v(ga1), it.base + k);
+      row_store<true>(a.ga1_out, pack_bf16x8v(ga1), it.base + k);
     (void)rh;
     if constexpr (NK == NORM_GLN) {
       ts += s;

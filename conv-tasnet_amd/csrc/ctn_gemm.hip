@@ -439,34 +439,10 @@ template <> CTN_DEV int cswz<float>(int row, int col) { return row * ColsPitch<f
 // own LDS stages, and add their 128x128 accumulators through LDS at the end: one
 // partial per chunk from 8 waves halves the partial-sum traffic (write here, read
 // by the slab reduction) of 4-wave workgroups at the same occupancy.
-#ifndef CTN_COLS_CKS
-#define CTN_COLS_CKS 2   // bf16 k-split groups per workgroup (experiment switch)
-#endif
-template <typename T> struct ColsCks { static constexpr int v = sizeof(T) == 2 ? CTN_COLS_CKS : 2; };
-// 1 (experiment switch): the B-operand loads carry the nontemporal hint
-#ifndef CTN_COLS_NTA
-#define CTN_COLS_NTA 0   // 1 (experiment switch): the A-operand loads carry the nontemporal hint
-#endif
-#ifndef CTN_COLS_NTB
-#define CTN_COLS_NTB 0
-#endif
-#ifndef CTN_COLS_XLM
-#define CTN_COLS_XLM 0
-#endif
-#ifndef CTN_COLS_CKR
-#define CTN_COLS_CKR 32  // bf16 frame rows per k-step (experiment switch: 32 or 64)
-#endif
-template <typename T> struct ColsCkr { static constexpr int v = sizeof(T) == 2 ? CTN_COLS_CKR : CKR; };
-constexpr int CKS = 2;                           // k-split groups per workgroup (host-side sizing)
+constexpr int CKS = 2;                           // k-split groups per workgroup
 
-#ifndef CTN_COLS_PRIO
-#define CTN_COLS_PRIO 0
-#endif
 template <typename T, int OPA, int OPB, int NK>
-__global__ __launch_bounds__(256 * ColsCks<T>::v) void gemm_cols_kernel(GemmCols p) {
-  constexpr int CKS = ColsCks<T>::v;
-  constexpr int CKR = ColsCkr<T>::v;
-  static_assert(CKR % 32 == 0, "k-steps are whole 32-row MFMA steps");
+__global__ __launch_bounds__(256 * CKS) void gemm_cols_kernel(GemmCols p) {
   constexpr int PITCH = ColsPitch<T>::v;
   constexpr int STAGE = 2 * CKR * PITCH;         // one k-step: A tile then B tile
   static_assert(CKS * 2 * STAGE >= CBP * CBQ * 4, "accumulator exchange (one group at a time) fits the stages");
@@ -476,9 +452,6 @@ __global__ __launch_bounds__(256 * ColsCks<T>::v) void gemm_cols_kernel(GemmCols
   constexpr int NCH = CKR * CPR / 256;           // chunks per thread per operand
   const int grp = threadIdx.x >> 8;              // k-split group
   char* smem = smem_all + grp * 2 * STAGE;
-  // static priority of one k-split group (experiment): 1 = group 1, 2 = group 0
-  if constexpr (CTN_COLS_PRIO == 1) { if (grp == 1) __builtin_amdgcn_s_setprio(1); }
-  if constexpr (CTN_COLS_PRIO == 2) { if (grp == 0) __builtin_amdgcn_s_setprio(1); }
   const int tid = threadIdx.x & 255, lane = tid & 63, wid = tid >> 6;
   const int wp = wid >> 1, wq = wid & 1;
   const int lr = lane & 15, lg = lane >> 4;
@@ -535,8 +508,8 @@ __global__ __launch_bounds__(256 * ColsCks<T>::v) void gemm_cols_kernel(GemmCols
       const int c = tid + 256 * i, rl = c / CPR;
       const int r = r0 + rl;
       // unconditional loads (clamped column; zeroed in swrite) keep the loop branch-free
-      R.a[i] = ldg16h<CTN_COLS_NTA != 0>(A + (size_t)r * p.lda + (pin ? p0 + cc0 * E : 0));
-      R.b[i] = ldg16h<CTN_COLS_NTB != 0>(B + (size_t)r * p.ldb + (qin ? q0 + cc0 * E : 0));
+      R.a[i] = ldg16(A + (size_t)r * p.lda + (pin ? p0 + cc0 * E : 0));
+      R.b[i] = ldg16(B + (size_t)r * p.ldb + (qin ? q0 + cc0 * E : 0));
       if constexpr (NK == NORM_CLN) {
         if constexpr (OPA != OP_PLAIN) R.sa[i] = *reinterpret_cast<const f32x2_t*>(p.aop.stats + r);
         if constexpr (OPB != OP_PLAIN) R.sb[i] = *reinterpret_cast<const f32x2_t*>(p.bop.stats + r);
@@ -664,10 +637,7 @@ __global__ __launch_bounds__(256 * ColsCks<T>::v) void gemm_cols_kernel(GemmCols
   // previous barrier).  The loop is unrolled by NSET so every set index is static.
   // Rows of padded frames are zero in the plain operands of this path, so they add
   // nothing; transformed operands are zeroed there explicitly.
-#ifndef CTN_COLS_NSET
-#define CTN_COLS_NSET 2
-#endif
-  constexpr int NSET = CTN_COLS_NSET;   // register sets in flight (experiment switch)
+  constexpr int NSET = 2;   // register sets in flight
   // Both groups run nks_all rounds in lock step (the barriers are workgroup-wide);
   // a group with fewer steps keeps staging its clamped last step but skips the
   // MFMAs of the surplus rounds (a wave-uniform branch after the barrier).
@@ -708,8 +678,7 @@ __global__ __launch_bounds__(256 * ColsCks<T>::v) void gemm_cols_kernel(GemmCols
   // consecutively (a lane-major image put every lane of a wave on the same four banks)
   float* xch = reinterpret_cast<float*>(smem_all);
   static_assert(16 * 256 * 4 * sizeof(float) <= sizeof(smem_all), "exchange image fits the stages");
-  // (CTN_COLS_XLM=1: the old lane-major image, for A/B runs)
-  auto xi = [&](int a) { return CTN_COLS_XLM ? (tid * 16 + a) * 4 : (a * 256 + tid) * 4; };
+  auto xi = [&](int a) { return (a * 256 + tid) * 4; };
   for (int g = 1; g < CKS; ++g) {
     if (grp == g) {
 #pragma unroll
@@ -734,21 +703,12 @@ __global__ __launch_bounds__(256 * ColsCks<T>::v) void gemm_cols_kernel(GemmCols
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      if constexpr (CTN_PART_NT == 2) {   // lane (lg, 4q + t): row lg*4 + t, columns 4q .. 4q+3
-        const int qq = q0 + wq * 64 + j * 16 + (lr & ~3);
-        if (qq >= p.Q) continue;          // whole quads (Q % 8 == 0)
-        float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-        quad_transpose4(v);
-        const int pr = p0 + wp * 64 + i * 16 + lg * 4 + (lr & 3);
-        if (pr < p.P) stg16h<true>(&Cp[(size_t)pr * p.Q + qq], f4bits(v));
-      } else {
-        const int qq = q0 + wq * 64 + j * 16 + lr;
-        if (qq >= p.Q) continue;
+      const int qq = q0 + wq * 64 + j * 16 + lr;
+      if (qq >= p.Q) continue;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const int pr = p0 + wp * 64 + i * 16 + lg * 4 + e;
-          if (pr < p.P) st_part(&Cp[(size_t)pr * p.Q + qq], acc[i][j][e]);
-        }
+      for (int e = 0; e < 4; ++e) {
+        const int pr = p0 + wp * 64 + i * 16 + lg * 4 + e;
+        if (pr < p.P) st_part<true>(&Cp[(size_t)pr * p.Q + qq], acc[i][j][e]);
       }
     }
 }
@@ -776,7 +736,7 @@ int gemm_cols_default_chunks(const GemmCols& p) {
 template <typename T, int OPA, int OPB, int NK>
 static hipError_t launch_cols_t(const GemmCols& p, hipStream_t s) {
   const int tiles = ((p.P + CBP - 1) / CBP) * ((p.Q + CBQ - 1) / CBQ);
-  hipLaunchKernelGGL((gemm_cols_kernel<T, OPA, OPB, NK>), dim3(tiles * p.nchunks), dim3(256 * ColsCks<T>::v), 0, s, p);
+  hipLaunchKernelGGL((gemm_cols_kernel<T, OPA, OPB, NK>), dim3(tiles * p.nchunks), dim3(256 * CKS), 0, s, p);
   return hipGetLastError();
 }
 
@@ -797,7 +757,7 @@ int gemm_cols_chunks(DType dt, const GemmCols& p) {
 
 hipError_t launch_gemm_cols(DType dt, const GemmCols& p, hipStream_t s) {
   if (gemm_cols_ws_eligible(dt, p) && p.nchunks == gemm_cols_ws_ranges(p)) return launch_gemm_cols_ws(p, s);
-  if (p.g.Kp % (dt == BF16 ? ColsCkr<bf16raw>::v : CKR) != 0 || p.P % 8 != 0 || p.Q % 8 != 0 || p.nchunks < 1 || p.g.rows() >= (1L << 31))
+  if (p.g.Kp % CKR != 0 || p.P % 8 != 0 || p.Q % 8 != 0 || p.nchunks < 1 || p.g.rows() >= (1L << 31))
     return hipErrorInvalidValue;
   const int nk = p.bop.kind != OP_PLAIN ? p.bop.norm : 0;
   if (dt == BF16)

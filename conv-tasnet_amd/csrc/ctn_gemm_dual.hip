@@ -39,55 +39,7 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 constexpr int DU_WV = 8, DU_NT = 512, DU_TM = 32, DU_GRID = 256;
 constexpr int DU_MMAX = 512;   // utterances whose gLN statistics a workgroup holds in LDS
 
-// Bound-finding experiments only (tools/microbench/dual_bench.hip): bit 0 drops the
-// row-part stores, 1 the A loads, 2 the row-part MFMAs, 3 the column part (reads and
-// MFMAs), 4 the Bm loads, 5 fences the epilogue off the MFMAs, 6 drops the LDS staging.
-#ifndef CTN_DU_EXP
-#define CTN_DU_EXP 0
-#endif
-#ifndef CTN_DU_DA
-#define CTN_DU_DA 4   // LDS ring depth of the (256 -> 512, norm-backward) pair
-#endif
-// cLN per-row statistics: 1 = a 4-byte LDS-DMA per wave and tile into a per-wave ring,
-// with no LDS-DMA in flight while the epilogue runs (vmcnt(0) before it); 0 = plain
-// loads from L2 at the point of use (their compiler-counted waits drain the ring
-// before every use).  Both reproducible run to run; 1 is faster.
-#ifndef CTN_DU_CST_DMA
-#define CTN_DU_CST_DMA 1
-#endif
-// cLN per-row sums across the four lane rows: 1 = v_permlane16/32_swap (VALU),
-// 0 = ds_bpermute (wrong sums in every launch while LDS-DMA is in flight, §10)
-#ifndef CTN_DU_PERMLANE
-#define CTN_DU_PERMLANE 1
-#endif
-// Reproducibility experiments (tools/microbench/dual_det.hip), all off:
-//   CTN_DU_DBG bit 0 vmcnt(0) before each epilogue, bit 1 vmcnt(0) at the loop top,
-//     bit 2 lgkmcnt(0) after each cross-lane step of the cLN row sums, bit 3
-//     lgkmcnt(0) after the epilogue's statistics and raw-row LDS reads, bit 4
-//     vmcnt(0) right after the cLN statistics store;
-//   CTN_DU_LATE 1: each iteration issues its DMA group after the epilogue;
-//   CTN_DU_NOCLAMP 1: the last D-1 iterations issue no DMA (default: they re-issue
-//     the range's last tile into its own slot, same bytes).
-#ifndef CTN_DU_DBG
-#define CTN_DU_DBG 0
-#endif
-// experiment: 1 raises the wave priority (s_setprio 1) while it issues a tile's MFMAs
-#ifndef CTN_DU_PRIO
-#define CTN_DU_PRIO 0
-#endif
-// 1: the resident weight and constants are loaded and waited for before the first DMA
-// groups are issued (round-2 order); 0 (experiment): the first D-1 DMA groups go out
-// first, so their latency overlaps the weight's.  0 makes the cLN epilogue statistics
-// of the first tiles irreproducible in every launch and gains nothing.
-#ifndef CTN_DU_EARLY
-#define CTN_DU_EARLY 1
-#endif
-#ifndef CTN_DU_LATE
-#define CTN_DU_LATE 0
-#endif
-#ifndef CTN_DU_NOCLAMP
-#define CTN_DU_NOCLAMP 0
-#endif
+constexpr int DU_DA = 4;       // LDS ring depth of the (256 -> 512, norm-backward) pair
 
 // LDS images (byte offsets), all checked conflict-free (bank model of
 // MI355X_MICROARCH.md §LDS) for the staging stores, the row part's ds_read_b128
@@ -166,8 +118,11 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
   constexpr int WN = NSB / 4;          // col-part waves along n (4 n-blocks each)
   constexpr bool BXF = OPB != OP_PLAIN;                 // Bm transformed in LDS
   constexpr bool GST = NK == NORM_GLN && (BXF || EPI == EPI_NORM_BWD);   // per-utterance stats table
-  constexpr bool CST = NK == NORM_CLN && (BXF || EPI == EPI_NORM_BWD) && CTN_DU_CST_DMA;   // per-row stats by DMA
-  constexpr bool CSG = NK == NORM_CLN && (BXF || EPI == EPI_NORM_BWD) && !CTN_DU_CST_DMA;  // per-row stats from L2
+  // cLN per-row statistics: a 4-byte LDS-DMA per wave and tile into a per-wave ring, with
+  // no LDS-DMA in flight while the epilogue runs (vmcnt(0) before it); faster than plain
+  // loads from L2 at the point of use, whose compiler-counted waits drain the ring before
+  // every use
+  constexpr bool CST = NK == NORM_CLN && (BXF || EPI == EPI_NORM_BWD);
   constexpr int A_SZ = TM * KR * 2, B_SZ = TM * NS * 2;
   constexpr int GA = A_SZ / 1024 / WV;                 // A blocks per wave per tile
   constexpr int G = GA + 1 + (CST ? 1 : 0);            // DMA instructions per wave per tile
@@ -260,7 +215,6 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
   }
   auto clampt = [&](int t) __attribute__((always_inline)) { return t < t1 ? t : t1 - 1; };
   auto dma = [&](int t) __attribute__((always_inline)) {   // group of tile t -> slot t % D
-    if constexpr (CTN_DU_EXP & 2) return;
     const int slot = t % D, tk = (t * TM) % Kp;
 #pragma unroll
     for (int u = 0; u < GA; ++u) {
@@ -280,27 +234,19 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
   // operations issued after it, by the fixed per-iteration order
   // [C store (k >= 1), DMA group (G, only for tiles < t1), statistics store (SST)]
   auto ops_after = [&](int tq, int t) __attribute__((always_inline)) {
-    const int nt = t1 - t0;
-    const int j = (CTN_DU_NOCLAMP && tq > t1 - 1 ? t1 - 1 : tq) - t0, k = t - t0;
-    auto grp = [&](int jj) { return CTN_DU_NOCLAMP && jj >= nt ? 0 : G; };
+    const int j = tq - t0, k = t - t0;
     int n = 0, kfrom;
     if (j <= D - 2) {
-      for (int jj = j + 1; jj <= D - 2; ++jj) n += grp(jj);
+      for (int jj = j + 1; jj <= D - 2; ++jj) n += G;
       kfrom = 0;
     } else {
-      n = CTN_DU_LATE ? 0 : SST;   // ops of group j's own iteration issued after it
+      n = SST;   // ops of group j's own iteration issued after it
       kfrom = j - D + 2;
     }
-    for (int kk = kfrom; kk < k; ++kk) n += (kk >= 1 ? 1 : 0) + grp(kk + D - 1) + SST;
+    for (int kk = kfrom; kk < k; ++kk) n += (kk >= 1 ? 1 : 0) + G + SST;
     return n;
   };
 
-  // CTN_DU_EARLY 0 (experiment): the first D-1 DMA groups go out before the resident
-  // weight and the constants are loaded
-  if (!CTN_DU_EARLY && t0 < t1)
-    for (int i = 0; i < D - 1; ++i)
-      if (!CTN_DU_NOCLAMP) dma(clampt(t0 + i));
-      else if (t0 + i < t1) dma(t0 + i);
   v4u wf[NBW][KB];
   // from the fragment-ordered copy when there is one (1 KiB contiguous per wave and
   // fragment, as in gemm_ws)
@@ -310,8 +256,7 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
     const int n = n0 + nbg * 16 * NBW + (lr >> 2) * NV + nb * 4 + (lr & 3);
 #pragma unroll
     for (int kb = 0; kb < KB; ++kb)
-      if constexpr (CTN_DU_EXP & 256) wf[nb][kb] = v4u{(uint32_t)n, (uint32_t)kb, 0u, 0u};   // no weight loads
-      else if (WF) wf[nb][kb] = ldg16(WF + frag_offset(sl * WNB + nbg, nb, kb, lane, KR));
+      if (WF) wf[nb][kb] = ldg16(WF + frag_offset(sl * WNB + nbg, nb, kb, lane, KR));
       else wf[nb][kb] = ldg16(W + (size_t)n * p.ldw + kb * 32 + lg * 8);
   }
   const float eal = EPI == EPI_NORM_BWD ? p.alpha[0] : 0.f;
@@ -369,13 +314,11 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
   // statistics of frame row r (tile-relative rt) of tile t whose ring slot is `slot`
   auto row_stat = [&](int t, int slot, int rt) __attribute__((always_inline)) {
     if constexpr (GST) return su[(t * TM) / Kp];
-    else if constexpr (CSG) return p.stats[t * TM + rt];
     else return *reinterpret_cast<const float2*>(smem + OFF_ST + (slot * WV + wid) * 256 + rt * 8);
   };
 
   auto transform = [&](auto le1, int t) __attribute__((always_inline)) {   // raw Bm(t) -> B image (t & 1)
     constexpr bool LE1 = decltype(le1)::value;
-    if constexpr (CTN_DU_EXP & 16) return;
     const int slot = t % D;
     v4u v = *reinterpret_cast<const v4u*>(smem + OFF_B + slot * B_SZ + xrd);
     const float2 st = row_stat(t, slot, xrow);
@@ -399,7 +342,6 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
   };
 
   auto compute = [&](int t, f32x4_t (&acc)[NBW]) __attribute__((always_inline)) {
-    if constexpr (CTN_DU_PRIO) __builtin_amdgcn_s_setprio(1);
     const char* a = smem + OFF_A + (t % D) * A_SZ;
     const char* bsl = BXF ? smem + OFF_BI + (t & 1) * B_SZ : smem + OFF_B + (t % D) * B_SZ;
 #pragma unroll
@@ -409,11 +351,9 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
       const v4u b = *reinterpret_cast<const v4u*>(a + rbase + kb * 1024);
 #pragma unroll
       for (int nb = 0; nb < NBW; ++nb)
-        if constexpr (CTN_DU_EXP & 4) acc[nb][kb & 3] += __uint_as_float(b[0] ^ wf[nb][kb][1]);
-        else acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf[nb][kb]),
+        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, wf[nb][kb]),
                                                           __builtin_bit_cast(bf16x8_t, b), acc[nb], 0, 0, 0);
     }
-    if constexpr (CTN_DU_EXP & 8) return;
     bf16x8_t af[4], bfr[4];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -431,16 +371,11 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
         dacc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfr[j], dacc[i][j], 0, 0, 0);
-    if constexpr (CTN_DU_PRIO) __builtin_amdgcn_s_setprio(0);
   };
 
   // row epilogue of tile t: lane holds row t*TM + erow, channels colbase..+NV -> C image (t & 1)
   auto epilogue = [&](auto le1, int t, const f32x4_t (&acc)[NBW]) __attribute__((always_inline)) {
     constexpr bool LE1 = decltype(le1)::value;
-    if constexpr (CTN_DU_EXP & 64) {
-      *reinterpret_cast<float*>(smem + OFF_C + (t & 1) * B_SZ + cw) = acc[0][0];
-      return;
-    }
     const int slot = t % D;
     f32x2_t v2[NV / 2];
 #pragma unroll
@@ -451,7 +386,6 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
     uint32_t rw[NV / 2];
     if constexpr (NV == 8) {
       const v4u r4 = *reinterpret_cast<const v4u*>(smem + (BXF ? OFF_B : OFF_R) + slot * B_SZ + rdo);
-      if constexpr (CTN_DU_DBG & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       rw[0] = r4[0]; rw[1] = r4[1]; rw[2] = r4[2]; rw[3] = r4[3];
     } else {
       const uint2 r2 = *reinterpret_cast<const uint2*>(smem + (BXF ? OFF_B : OFF_R) + slot * B_SZ + rdo);
@@ -463,7 +397,6 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
       for (int c = 0; c < NV / 2; ++c) v2[c] += f32x2_t{__uint_as_float(rw[c] << 16), __uint_as_float(rw[c] & 0xffff0000u)};
     } else {
       const float2 est = row_stat(t, slot, erow);
-      if constexpr (CTN_DU_DBG & 8) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       const f32x2_t rs = {est.y, est.y}, ms = {-est.x * est.y, -est.x * est.y};
 #pragma unroll
       for (int c = 0; c < NV / 2; ++c) {
@@ -491,18 +424,12 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
         run_m = m;
         run_slab[m - m0] = make_double2(run_s, run_q);
       } else {
+        // VALU lane swaps: a ds_bpermute row sum is wrong in every launch while LDS-DMA is
+        // in flight
         float s = s2[0] + s2[1], ss = q2[0] + q2[1];
-#if CTN_DU_PERMLANE
         s = xsum_rows(s);
         ss = xsum_rows(ss);
-#else
-        s += __shfl_xor(s, 16, 64); ss += __shfl_xor(ss, 16, 64);
-        if constexpr (CTN_DU_DBG & 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        s += __shfl_xor(s, 32, 64); ss += __shfl_xor(ss, 32, 64);
-        if constexpr (CTN_DU_DBG & 4) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
         p.grp_slab[(size_t)(t * TM + erow) * (S * WNB) + sl * WNB + nbg] = make_double2((double)s, (double)ss);
-        if constexpr (CTN_DU_DBG & 16) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
     }
   };
@@ -513,48 +440,37 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
     const uint32_t vo = cvo + (uint32_t)(t * TM * p.ldc * 2);   // soffset 0: see du_bstore
     if constexpr (CG == 8) {
       const v4u v = *reinterpret_cast<const v4u*>(src);
-      if constexpr (!(CTN_DU_EXP & 1)) __builtin_amdgcn_raw_buffer_store_b128(v, rC, vo, 0, 0);
-      else asm volatile("" ::"v"(v));
+      __builtin_amdgcn_raw_buffer_store_b128(v, rC, vo, 0, 0);
     } else {
       typedef uint32_t v2u __attribute__((ext_vector_type(2)));
       const v2u v = *reinterpret_cast<const v2u*>(src);
-      if constexpr (!(CTN_DU_EXP & 1)) __builtin_amdgcn_raw_buffer_store_b64(v, rC, vo, 0, 0);
-      else asm volatile("" ::"v"(v));
+      __builtin_amdgcn_raw_buffer_store_b64(v, rC, vo, 0, 0);
     }
   };
 
   auto run = [&](auto le1) __attribute__((always_inline)) {
     f32x4_t acc[NBW];
-    if (CTN_DU_EARLY)
-      for (int i = 0; i < D - 1; ++i)
-        if (!CTN_DU_NOCLAMP) dma(clampt(t0 + i));
-        else if (t0 + i < t1) dma(t0 + i);
+    // the resident weight and constants are loaded and waited for before the first DMA
+    // groups are issued: the other order makes the cLN epilogue statistics of the first
+    // tiles irreproducible in every launch and gains nothing
+    for (int i = 0; i < D - 1; ++i) dma(clampt(t0 + i));
     for (int t = t0; t < t1; ++t) {
       // BXF: the transform reads raw Bm of tile t+1 this iteration, so wait for its group
       const int tq = BXF ? t + 1 : t;
-      if constexpr (CTN_DU_DBG & 2) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      else if constexpr (!(CTN_DU_EXP & 128)) du_vmwait(ops_after(tq, t));
+      du_vmwait(ops_after(tq, t));
       if (BXF && t == t0) {   // the first tile's raw rows: transform them before everything
         lds_barrier();
         transform(le1, t0);
       }
       lds_barrier();
       if (t > t0) store_c(t - 1);
-      if (!CTN_DU_LATE) {
-        if (!CTN_DU_NOCLAMP) dma(clampt(t + D - 1));
-        else if (t + D - 1 < t1) dma(t + D - 1);
-      }
+      dma(clampt(t + D - 1));   // past the range: the last tile again into its own slot, same bytes
       if constexpr (BXF) transform(le1, clampt(t + 1));
       compute(t, acc);
-      if constexpr (CTN_DU_EXP & 32) __builtin_amdgcn_sched_barrier(0);
       // cLN with DMA'd row statistics: no LDS-DMA in flight while the epilogue reads
       // its LDS operands (the one configuration measured reproducible)
-      if constexpr (CST || (CTN_DU_DBG & 1)) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if constexpr (CST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       epilogue(le1, t, acc);
-      if (CTN_DU_LATE) {   // after the epilogue: its slot (t-1)%D was last read before this phase's barrier
-        if (!CTN_DU_NOCLAMP) dma(clampt(t + D - 1));
-        else if (t + D - 1 < t1) dma(t + D - 1);
-      }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no DMA may land after the workgroup ends
     lds_barrier();
@@ -576,8 +492,7 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
       const int n = n0 + (wn * 4 + j) * 16 + lr;
 #pragma unroll
       for (int e = 0; e < 4; ++e)
-        if constexpr (CTN_DU_EXP & 512) asm volatile("" ::"v"(dacc[i][j][e]));   // timing: no D partial stores
-        else Dp[(size_t)((wp * 4 + i) * 16 + 4 * lg + e) * p.Nout + n] = dacc[i][j][e];
+        Dp[(size_t)((wp * 4 + i) * 16 + 4 * lg + e) * p.Nout + n] = dacc[i][j][e];
     }
 }
 
@@ -589,7 +504,7 @@ __global__ __launch_bounds__(DU_NT) void gemm_dual_kernel(GemmDual p) {
 // (gh1.W1 + dW1); cleared bits run the row GEMM + column GEMM kernels.  Read on every
 // query so a process can compare both paths (tests/test_gpu_tblock.py).  Default 1:
 // pair A measures 109 us against 62 + 60 us for its two kernels; pair B 103 us against
-// 49 + 45 us (tools/microbench/dual_bench.hip), so B stays on the two kernels.
+// 49 + 45 us (microbenchmark), so B stays on the two kernels.
 static int dual_mask() {
   const char* e = getenv("CTN_GEMM_DUAL");
   return e ? atoi(e) : 1;
@@ -643,7 +558,7 @@ WsRuns gemm_dual_runs(const GemmDual& p) {
 int gemm_dual_group_parts(const GemmDual& p) {
   int kb, nsb, nbw;
   dual_shape(p.Kred, p.Nout, &kb, &nsb, &nbw);
-  if (p.norm != NORM_GLN)   // per (slice, row wave), or per slice (ctn_dual_ws.hip, CTN_DV_CLNC)
+  if (p.norm != NORM_GLN)   // per (slice, row wave), or per slice (ctn_dual_ws.hip)
     return dual_slices(p) * (gemm_dual_ws_eligible(p) ? dual_ws_cln_parts_per_slice() : nsb / nbw);
   const WsRuns w = gemm_dual_runs(p);
   const long entries = (long)w.grid * w.waves * w.kmax;
@@ -668,7 +583,7 @@ template <int NK>
 static hipError_t dual_launch_nk(const GemmDual& p, hipStream_t s) {
   const dim3 grid(gemm_dual_ranges(p) * dual_slices(p));
   if (p.Kred == 256 && p.epi == EPI_NORM_BWD && p.bop.kind == OP_PRELU_NORM)
-    hipLaunchKernelGGL((gemm_dual_kernel<8, 8, 2, EPI_NORM_BWD, OP_PRELU_NORM, NK, CTN_DU_DA>), grid, dim3(DU_NT), 0, s, p);
+    hipLaunchKernelGGL((gemm_dual_kernel<8, 8, 2, EPI_NORM_BWD, OP_PRELU_NORM, NK, DU_DA>), grid, dim3(DU_NT), 0, s, p);
   else if (p.Kred == 512 && p.epi == EPI_RESID && p.bop.kind == OP_PLAIN)
     hipLaunchKernelGGL((gemm_dual_kernel<16, 4, 1, EPI_RESID, OP_PLAIN, NORM_GLN, 3>), grid, dim3(DU_NT), 0, s, p);
   else

@@ -31,113 +31,38 @@ namespace ctn {
 typedef short bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
-#ifndef CTN_WS_GRID
-#define CTN_WS_GRID 256
-#endif
-constexpr int WS_WAVES = 8, WS_TM = 16, WS_GRID = CTN_WS_GRID;
+constexpr int WS_WAVES = 8, WS_TM = 16, WS_GRID = 256;
 // Plain-operand configurations without a residual stream (the forward 1x1 conv, the
-// mask conv) take their tiles by LDS-DMA into a WS_DR-deep ring (CTN_WS_DMA=0: the
-// register-staged pipeline, for A/B builds)
-#ifndef CTN_WS_DMA
-#define CTN_WS_DMA 1
-#endif
-#ifndef CTN_WS_DR
-#define CTN_WS_DR 6   // 4: 41.9/42.0 us, 6: 40.8/41.2 (forward B -> H, profiles/r05/nt_exp/r5s512_*)
-#endif
-constexpr int WS_DR = CTN_WS_DR;
-// The LDS-DMA ring's hand-offs (gLN, no in-kernel cLN finalize): 1 = generation words per
-// slot and wave instead of one workgroup barrier per tile — a wave starts tile t's MFMAs
-// once every wave's DMA of tile t has landed and refills a slot once every wave has read
-// it, so the waves may drift within the ring.  Measured slower (forward 1x1 35.4 ->
-// 40.6 / 41.7 / 43.0 us at rings of 4 / 6 / 8 tiles): 0 (default) keeps the
-// barrier.
-#ifndef CTN_WS_FLAGS
-#define CTN_WS_FLAGS 0
-#endif
+// mask conv) take their tiles by LDS-DMA into a WS_DR-deep ring, handed off by one
+// workgroup barrier per tile (generation words per slot and wave measured slower:
+// forward 1x1 35.4 -> 40.6 / 41.7 / 43.0 us at rings of 4 / 6 / 8 tiles)
+constexpr int WS_DR = 6;   // 4: 41.9/42.0 us, 6: 40.8/41.2 (forward B -> H, profiles/r05/nt_exp/r5s512_*)
 constexpr int WS_FOLD_MAX = 512;   // utterances whose gLN operand stats a workgroup holds in LDS
 
 // Bound-finding experiments only (tools/microbench): bit 0 drops the output
 // stores, bit 1 the A-tile loads, bit 2 the MFMAs, bit 3 the epilogue math, bit 7 the
-// resident weight's loads, bit 10 the dL/dh1 stores of the norm-1-backward form; bit 6
-// (experiment, not bound-finding) lets the scheduler move epilogue math into the MFMAs.
+// resident weight's loads, bit 10 the dL/dh1 stores of the norm-1-backward form.
 #ifndef CTN_WS_EXP
 #define CTN_WS_EXP 0
 #endif
 // A-tile register ring depth (tiles whose loads are in flight while one is staged)
-// of the 16-wave and 8-wave non-interleaved configurations
-#ifndef CTN_WS_PF16
-#define CTN_WS_PF16 1
-#endif
-#ifndef CTN_WS_PF8
-#define CTN_WS_PF8 1
-#endif
-// Issue order inside a tile iteration of the non-interleaved configurations.
-// gfx9 retires loads and stores in one in-order vmcnt queue, so a load issued
-// behind a tile's output stores cannot be consumed before those stores are
-// acknowledged.  1: stage(t+1) and the loads of the next tiles go BEFORE the output
-// stores of tile t (which are written last); 0: the original order (stores, then
-// the next loads).
-// Output-channel slices of the Nout = 512 forward GEMM: 2 = two independent
-// 8-wave workgroups per CU, each holding half the weight (the A tile is read by
-// both from the XCD's L2), instead of one 16-wave workgroup.
-#ifndef CTN_WS_S512
-#define CTN_WS_S512 1
-#endif
+// of the non-interleaved configurations
+constexpr int WS_PF = 1;
 // LDS fragment look-ahead of the MFMA loop, in k-steps
 // (16 waves: plain-operand configurations only; 1 = one k-step ahead, 124 VGPRs without
 // spills for the forward B -> H GEMM: 36.1 -> 34.5 us, microbenchmark, round 6; the
 // transformed-operand 16-wave configurations spill more with it)
-#ifndef CTN_WS_LA16
-#define CTN_WS_LA16 1
-#endif
-#ifndef CTN_WS_LA8
-#define CTN_WS_LA8 3
-#endif
-// experiment: 1 raises the wave priority (s_setprio 1) while it issues a tile's MFMAs
-// Nontemporal hints per configuration (bits): 1 = the resident-weight loads of the
-// forward B -> H GEMM (plain operand, PReLU-statistics epilogue), 2 = the output stores
-// of the forward H -> B GEMM (norm-2 operand, residual epilogue), 4 = the output (h1)
-// stores of the forward B -> H GEMM, 8 = the dL/dh1 stores of the data-gradient GEMM
-// (norm-1-backward operand), 16 = that GEMM's output (gx) stores, 32 = that GEMM's
-// dL/da1 operand loads, 64 = its h1 loads (both their last use), 128 = the H -> B GEMM's d
-// loads, 256 = the residual loads (x in the H -> B GEMM, gy in the gx GEMM).  Bit 32 measured
-// -1.7 us, bit 64 -2 us in the column GEMM after it; the others slower or flat
+constexpr int WS_LA16 = 1, WS_LA8 = 3;
+// Nontemporal hints of the data-gradient GEMM's (norm-1-backward operand) dL/da1 and h1
+// operand loads, both their last use: -1.7 us, and -2 us in the column GEMM after it; the
+// hints tried at the seven other load and store sites measured slower or flat
 // (profiles/r05/nt_exp/)
-#ifndef CTN_WS_NT
-#define CTN_WS_NT 96
-#endif
-#ifndef CTN_WS_PRIO
-#define CTN_WS_PRIO 0
-#endif
-// Ping-pong (LDS-DMA ring configurations of 16 waves): waves 8-15 run each tile half a
-// tile behind waves 0-7 — two barriers per tile, and between them one half runs its MFMAs
-// while the other runs the previous tile's epilogue and stores, so on every SIMD (two
-// waves of each half) the matrix pipe and the vector/store issue overlap instead of all
-// 16 waves meeting at one barrier and then running the same phase.  Same arithmetic,
-// same results bit for bit.
-#ifndef CTN_WS_PP
-#define CTN_WS_PP 0
-#endif
-#ifndef CTN_WS_HPRIO
-#define CTN_WS_HPRIO 0
-#endif
+constexpr bool WS_NT_GA1 = true, WS_NT_H1 = true;
 #ifndef CTN_WS_STAMP
 #define CTN_WS_STAMP 0
 #endif
 #if CTN_WS_STAMP
 __device__ unsigned long long ws_stamps[256 * 16 * 8];
-#endif
-// 1: wait for the resident weight before the first tiles' loads are issued; 0
-// (experiment): after them.  Measured the same.
-// cLN statistics of 64 tiles per lane, broadcast by v_readlane (see load_a)
-#ifndef CTN_WS_CLN_BATCH
-#define CTN_WS_CLN_BATCH 1
-#endif
-#ifndef CTN_WS_EARLY
-#define CTN_WS_EARLY 1
-#endif
-#ifndef CTN_WS_ORDER
-#define CTN_WS_ORDER 1
 #endif
 
 // LDS byte offset of the 16-byte piece (frame row lr, k-chunk lg) of k-block kb
@@ -155,7 +80,7 @@ CTN_DEV void ready(float v) { asm volatile("" ::"v"(v)); }
 // S: output-channel slices; workgroup b -> (row range rr, slice sl), the S slices of
 // a range on one XCD (hardware ids are dealt round-robin over the 8 XCDs) so the A
 // tile comes from HBM once.  Each slice-workgroup holds NS = WV*16*NB channels.
-// (S = 2: two 8-wave slice workgroups share a CU, CTN_WS_S512; S = 3: the three 512-channel
+// (S = 2: two 8-wave slice workgroups share a CU, not dispatched; S = 3: the three 512-channel
 // slices of a 1536-channel output (c5's mask conv, C*N = 3*512) on three CUs of one XCD.)
 template <int OPK, int NK, int EPI, int NB, int KB, int WV, int MB, int S = 1>
 __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_kernel(GemmRows p) {
@@ -172,16 +97,13 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
   // one-tile register prefetch + two accumulator sets only where registers allow
   constexpr bool N1B = OPK == OP_NORM1_BWD;    // norm-1/PReLU-1 backward on the operand
   constexpr bool SWP = OPK == OP_PLAIN && WV == 8;
-  constexpr int PF = SWP ? 1 : (WV == 16 ? CTN_WS_PF16 : CTN_WS_PF8);
+  constexpr int PF = WS_PF;
   // cLN PReLU statistics finalized in the kernel: per-row partials of the WV waves of
   // one tile meet in LDS and are summed after the next barrier (tile parity buffers)
   constexpr bool CLN_FIN = EPI == EPI_PRELU_STATS && NK == NORM_CLN && !SWP && S == 1;
   __shared__ double2 scln[CLN_FIN ? 2 * TM * WV : 1];
-  constexpr bool WDMA = CTN_WS_DMA && OPK == OP_PLAIN && !SWP && EPI != EPI_RESID && EPI != EPI_NORM_BWD;
+  constexpr bool WDMA = OPK == OP_PLAIN && !SWP && EPI != EPI_RESID && EPI != EPI_NORM_BWD;
   __shared__ __attribute__((aligned(16))) char sA[WDMA ? WS_DR : 2][TM * KR * 2];
-  constexpr bool WFL = WDMA && CTN_WS_FLAGS && !CLN_FIN && WV % 4 == 0;   // flag-ring hand-offs
-  __shared__ __attribute__((aligned(16))) uint32_t fl_full[WFL ? WS_DR : 1][WFL ? WV : 4];
-  __shared__ __attribute__((aligned(16))) uint32_t fl_done[WFL ? WS_DR : 1][WFL ? WV : 4];
   __shared__ float sgam[EPI == EPI_NORM_BWD ? NB * 16 * WV : 1];
   // gLN operand statistics, one pair per utterance, finalized here (StatFold)
   constexpr bool FOLDS = NK == NORM_GLN && OPK != OP_PLAIN;
@@ -191,9 +113,6 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
 
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int lr = lane & 15, lg = lane >> 4;
-  // static priority for the second half of the waves (experiment; the younger half loses
-  // every issue arbitration otherwise, MI355X_MICROARCH.md "Two waves per SIMD" item 4)
-  if constexpr (CTN_WS_HPRIO != 0) { if (wid >= WV / 2) __builtin_amdgcn_s_setprio(CTN_WS_HPRIO); }
   const int ntile = (int)(p.g.rows() / TM);
   constexpr int NS = WV * 16 * NB;             // output channels per slice
   const int nr = (int)gridDim.x / S;           // row ranges
@@ -222,18 +141,13 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
   // fragment: half the L2 lines of the row-major reads, whose 64-byte row pieces fill
   // only half of each line; every CU reads the whole weight, so this read is a fixed
   // cost of the launch, 12.9 -> 7.8 us at one tile per workgroup)
-  constexpr bool NTW = (CTN_WS_NT & 1) && OPK == OP_PLAIN && EPI == EPI_PRELU_STATS;
-  constexpr bool NTO = ((CTN_WS_NT & 2) && OPK == OP_PRELU_NORM) ||
-                      ((CTN_WS_NT & 4) && OPK == OP_PLAIN && EPI == EPI_PRELU_STATS) ||
-                      ((CTN_WS_NT & 16) && OPK == OP_NORM1_BWD);
-  constexpr bool NTG = (CTN_WS_NT & 8) != 0;
   v4u wf[NB][KB];
   const bf16raw* WF = NB == 2 ? reinterpret_cast<const bf16raw*>(p.Wf) : nullptr;
   if (WF) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
-      for (int kb = 0; kb < KB; ++kb) wf[nb][kb] = ldg16h<NTW>(WF + frag_offset(sl * WV + wid, nb, kb, lane, KR));
+      for (int kb = 0; kb < KB; ++kb) wf[nb][kb] = ldg16(WF + frag_offset(sl * WV + wid, nb, kb, lane, KR));
   } else {
 #pragma unroll
   for (int nb = 0; nb < NB; ++nb) {
@@ -245,7 +159,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
         const int kr = (CTN_WS_EXP & 512) ? (kb + (int)blockIdx.x) % KB : kb;
         if constexpr (CTN_WS_EXP & 256) wf[nb][kb] = ldg16(W + ((size_t)((wid * NB + nb) * KB + kr) * 64 + lane) * 8);
         else wf[nb][kb] = ldg16(W + (size_t)n * p.ldw + kr * 32 + lg * 8);
-      } else wf[nb][kb] = ldg16h<NTW>(W + (size_t)n * p.ldw + kb * 32 + lg * 8);
+      } else wf[nb][kb] = ldg16(W + (size_t)n * p.ldw + kb * 32 + lg * 8);
   }
   }
 
@@ -303,7 +217,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
   // cLN with wave-uniform rows (a row's 16-byte chunks span whole waves): the per-row
   // statistics (and N1B means) of 64 consecutive tiles are loaded one tile per lane and
   // broadcast with v_readlane, instead of a load per row and tile in the prefetch
-  constexpr bool CB = CTN_WS_CLN_BATCH && NK == NORM_CLN && OPK != OP_PLAIN && !FOLDS && CPR % 64 == 0;
+  constexpr bool CB = NK == NORM_CLN && OPK != OP_PLAIN && !FOLDS && CPR % 64 == 0;
   float2 bst[CB ? NA : 1], bsm[CB && N1B ? NA : 1];
   int bbase = -(1 << 29);
   auto batch_load = [&](int tb) __attribute__((always_inline)) {
@@ -329,9 +243,8 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
     for (int j = 0; j < NA; ++j) {
       const int r = t * TM + rl0 + j * RSTEP;
       if constexpr (CTN_WS_EXP & 2) ra[s][j] = v4u{(uint32_t)r, 0u, 0u, 0u};
-      else ra[s][j] = ldg16h<((CTN_WS_NT & 32) != 0 && N1B) || ((CTN_WS_NT & 128) != 0 && OPK == OP_PRELU_NORM)>(
-               A + (size_t)r * p.lda + kc * 8);
-      if constexpr (N1B) rh[s][j] = ldg16h<(CTN_WS_NT & 64) != 0>(H1 + (size_t)r * p.lda + kc * 8);
+      else ra[s][j] = ldg16h<WS_NT_GA1 && N1B>(A + (size_t)r * p.lda + kc * 8);
+      if constexpr (N1B) rh[s][j] = ldg16h<WS_NT_H1>(H1 + (size_t)r * p.lda + kc * 8);
       if constexpr (CB) {
       } else if constexpr (OPK != OP_PLAIN && !FOLDS && (CTN_WS_EXP & 2048)) {
         ast[s][j] = make_float2(0.1f, 1.3f);   // timing only: no statistics loads
@@ -417,7 +330,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
     if constexpr (N1B && !(CTN_WS_EXP & 1024)) {   // bit 10 (timing only): no dL/dh1 stores
       if (tu < t1) {
 #pragma unroll
-        for (int j = 0; j < NA; ++j) stg16h<NTG>(GH + (size_t)(tu * TM + rl0 + j * RSTEP) * p.lda + kc * 8, ghv[j]);
+        for (int j = 0; j < NA; ++j) stg16(GH + (size_t)(tu * TM + rl0 + j * RSTEP) * p.lda + kc * 8, ghv[j]);
       }
     }
   };
@@ -439,7 +352,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
       if constexpr (HAS_R) {
         const size_t off = (size_t)r * p.ldr + colbase;
 #pragma unroll
-        for (int q = 0; q < Q; ++q) rn[mb][q] = ldg16h<(CTN_WS_NT & 256) != 0>(Rp + off + q * 8);
+        for (int q = 0; q < Q; ++q) rn[mb][q] = ldg16(Rp + off + q * 8);
       }
       if constexpr (EPI == EPI_NORM_BWD) est[mb] = p.stats[stat_index<NK>(r, Kp)];
     }
@@ -448,9 +361,8 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
   // LDS fragment reads run LA k-steps ahead of the MFMAs that consume them (a
   // register window of LA+1 steps), so a k-step's MFMAs never wait on a read issued
   // just before them (one read in flight per step exposed the LDS latency 16x/tile).
-  constexpr int LA = SWP ? 0 : WV == 16 ? (OPK == OP_PLAIN ? CTN_WS_LA16 : 0) : CTN_WS_LA8;
+  constexpr int LA = SWP ? 0 : WV == 16 ? (OPK == OP_PLAIN ? WS_LA16 : 0) : WS_LA8;
   auto mfma_tile = [&](const char* buf, f32x4_t (&acc)[MB][NB]) __attribute__((always_inline)) {
-    if constexpr (CTN_WS_PRIO) __builtin_amdgcn_s_setprio(1);   // experiment: MFMA issue first
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
@@ -486,7 +398,6 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
         __builtin_amdgcn_sched_group_barrier(0x008, MB * NB, 0);
       }
     }
-    if constexpr (CTN_WS_PRIO) __builtin_amdgcn_s_setprio(0);
   };
 
   // gLN run partial of this wave (WsRuns layout); every lane stores the same value
@@ -513,7 +424,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
       bf16raw* dst = Cp + (size_t)(t * TM + mb * 16 + lr) * p.ldc + colbase;
 #pragma unroll
       for (int q = 0; q < Q; ++q)
-        if constexpr (!(CTN_WS_EXP & 1)) stg16h<NTO>(dst + q * 8, ov[mb][q]);
+        if constexpr (!(CTN_WS_EXP & 1)) stg16(dst + q * 8, ov[mb][q]);
     }
   };
   auto epilogue_math = [&](auto le1, int t, const f32x4_t (&acc)[MB][NB]) __attribute__((always_inline)) {
@@ -625,7 +536,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
   };
 
   // wait for the resident weight and the epilogue/operand constants once, before the
-  // tile loop (CTN_WS_EARLY)
+  // tile loop, ahead of the first tiles' loads (after them measured the same)
   auto ready_all = [&]() __attribute__((always_inline)) {
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb)
@@ -638,7 +549,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
     ready(oal);
     ready(eal);
   };
-  if constexpr (CTN_WS_EARLY) ready_all();
+  ready_all();
   if (t0 >= t1) {
     fold_stats();   // a workgroup without tiles still stores its utterances' pairs
     return;
@@ -703,79 +614,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
       auto mn = [](int a, int b) { return a < b ? a : b; };
       f32x4_t acc[MB][NB];
       fold_stats();
-      if constexpr (WFL) {
-        if (tid < WS_DR * WV) {
-          (&fl_full[0][0])[tid] = 0u;
-          (&fl_done[0][0])[tid] = 0u;
-        }
-        __syncthreads();
-      }
       for (int i = 0; i < WS_DR - 1; ++i) dma(t0 + i);
-      if constexpr (!CTN_WS_EARLY) ready_all();
-      if constexpr (WFL) {
-        // tile t in slot t % WS_DR, generation (t - t0) / WS_DR + 1 of that slot
-        for (int t = t0; t < t1; ++t) {
-          {
-            constexpr int NST = NFW * (WS_DR - 2) + SPT * (WS_DR - 1);   // steady state
-            const int n = NFW * mn(WS_DR - 2, t1 - 1 - t) + SPT * mn(WS_DR - 1, t - t0);
-            if (n == NST) vmwait_c<NST>();
-            else vmwait23(n);
-          }
-          const int slot = t % WS_DR;
-          const uint32_t gen = (uint32_t)((t - t0) / WS_DR + 1);
-          flag_signal(&fl_full[slot][wid], gen);   // this wave's DMA of tile t landed
-          flag_wait<WV>(fl_full[slot], gen, p.err);       // every wave's
-          mfma_tile(sA[slot], acc);
-          if constexpr (!(CTN_WS_EXP & 64)) __builtin_amdgcn_sched_barrier(0);
-          flag_signal(&fl_done[slot][wid], gen);   // this wave's reads of the slot done
-          const int tn = t + WS_DR - 1;            // into the slot of tile t - 1
-          if (tn < t1) {
-            if (t > t0) flag_wait<WV>(fl_done[(t - 1) % WS_DR], (uint32_t)((t - 1 - t0) / WS_DR + 1), p.err);
-            dma(tn);
-          }
-          epilogue_math(le1, t, acc);
-          store_out(t);
-        }
-      } else if constexpr (CTN_WS_PP && WV == 16) {
-        // ping-pong: half 0 (waves 0-7) MFMA(t) | epilogue(t); half 1 (waves 8-15)
-        // epilogue(t-1) | MFMA(t), the two phases of tile t separated by a barrier.  The
-        // slot refilled at iteration t (tile t-1's) was last read by half 1 in phase 2
-        // of iteration t-1, before this iteration's first barrier.
-        const bool late = wid >= WV / 2;
-        for (int t = t0; t < t1; ++t) {
-          {
-            // half 1 has stored nothing in iteration t0 (no tile t0 - 1): one store group
-            // fewer behind the DMA of tile t, so its count is one group stricter
-            constexpr int NST = NFW * (WS_DR - 2) + SPT * (WS_DR - 1);   // steady state
-            const int ds = t - t0 - (late ? 1 : 0);
-            const int n = NFW * mn(WS_DR - 2, t1 - 1 - t) + SPT * mn(WS_DR - 1, ds < 0 ? 0 : ds);
-            if (n == NST) vmwait_c<NST>();
-            else vmwait23(n);
-          }
-          lds_barrier();
-          dma(t + WS_DR - 1);
-          if (!late) {
-            mfma_tile(sA[t % WS_DR], acc);
-          } else if (t > t0) {
-            epilogue_math(le1, t - 1, acc);
-            store_out(t - 1);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-          lds_barrier();
-          if (t > t0) cln_final(t - 1);   // both halves' partials of tile t - 1 are in LDS
-          if (!late) {
-            epilogue_math(le1, t, acc);
-            store_out(t);
-          } else {
-            mfma_tile(sA[t % WS_DR], acc);
-          }
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        if (late) {
-          epilogue_math(le1, t1 - 1, acc);
-          store_out(t1 - 1);
-        }
-      } else
       for (int t = t0; t < t1; ++t) {
         {
           constexpr int NST = NFW * (WS_DR - 2) + SPT * (WS_DR - 1);   // steady state
@@ -787,7 +626,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
         if (t > t0) cln_final(t - 1);
         dma(t + WS_DR - 1);
         mfma_tile(sA[t % WS_DR], acc);
-        if constexpr (!(CTN_WS_EXP & 64)) __builtin_amdgcn_sched_barrier(0);
+        __builtin_amdgcn_sched_barrier(0);
         epilogue_math(le1, t, acc);
         store_out(t);
       }
@@ -800,7 +639,6 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
       stage(le1, t0, sA[t0 & 1], std::integral_constant<int, 0>{});
       store_gh(t0);
       load_a(clampt(t0 + PF), std::integral_constant<int, 0>{});
-      if constexpr (!CTN_WS_EARLY) ready_all();
       for (int tb = t0; tb < t1; tb += PF) {
         static_for<PF>([&](auto u) {
           constexpr int nx = (decltype(u)::value + 1) % PF;   // slot of tile t+1
@@ -811,28 +649,24 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
             if (t > t0) cln_final(t - 1);
             WS_STAMP(0);
             mfma_tile(sA[t & 1], acc);
-            if constexpr (!(CTN_WS_EXP & 64)) __builtin_amdgcn_sched_barrier(0);
+            __builtin_amdgcn_sched_barrier(0);
             WS_STAMP(1);
-            if constexpr (CTN_WS_ORDER == 1) {
-              // next tile's operand (its buffer's last reader finished before the barrier)
-              stage(le1, t + 1, sA[(t + 1) & 1], std::integral_constant<int, nx>{});
-              WS_STAMP(2);
-              load_a(clampt(t + 1 + PF), std::integral_constant<int, nx>{});
-              WS_STAMP(3);
-              epilogue_math(le1, t, acc);
-              WS_STAMP(4);
-              load_r(clampt(t + 1));   // rn(t) consumed above
-              WS_STAMP(5);
-              store_out(t);
-              store_gh(t + 1);
-              WS_STAMP(6);
-            } else {
-              epilogue(le1, t, acc);
-              load_r(clampt(t + 1));
-              stage(le1, t + 1, sA[(t + 1) & 1], std::integral_constant<int, nx>{});
-              store_gh(t + 1);
-              load_a(clampt(t + 1 + PF), std::integral_constant<int, nx>{});
-            }
+            // gfx9 retires loads and stores in one in-order vmcnt queue, so a load issued
+            // behind a tile's output stores cannot be consumed before those stores are
+            // acknowledged: stage(t+1) and the loads of the next tiles go BEFORE the output
+            // stores of tile t, which are written last.
+            // next tile's operand (its buffer's last reader finished before the barrier)
+            stage(le1, t + 1, sA[(t + 1) & 1], std::integral_constant<int, nx>{});
+            WS_STAMP(2);
+            load_a(clampt(t + 1 + PF), std::integral_constant<int, nx>{});
+            WS_STAMP(3);
+            epilogue_math(le1, t, acc);
+            WS_STAMP(4);
+            load_r(clampt(t + 1));   // rn(t) consumed above
+            WS_STAMP(5);
+            store_out(t);
+            store_gh(t + 1);
+            WS_STAMP(6);
           }
         });
       }
@@ -847,7 +681,6 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
       load_r(t0);
       stage(le1, t0 + 1, sA[(t0 + 1) & 1], std::integral_constant<int, 0>{});
       load_a(clampt(t0 + 2), std::integral_constant<int, 0>{});
-      if constexpr (!CTN_WS_EARLY) ready_all();
       // unrolled by two so the two accumulator sets swap roles without copies
       auto step = [&](int t, f32x4_t (&cur)[MB][NB], f32x4_t (&prev)[MB][NB]) __attribute__((always_inline)) {
         lds_barrier();
@@ -1003,12 +836,13 @@ static bool ws_wide(const GemmRows& p) {   // Nout = 512 (or 3 x 512) on 32-row 
 }
 static int ws_waves(const GemmRows& p) { return ws_wide(p) ? 16 * (p.Nout / 512) : 8; }
 static int ws_tile_rows(const GemmRows& p) { return ws_wide(p) ? 32 : WS_TM; }
-static int ws_slices(const GemmRows& p) { return p.Nout == 1536 ? 3 : ws_wide(p) ? CTN_WS_S512 : 1; }
+static int ws_slices(const GemmRows& p) { return p.Nout == 1536 ? 3 : 1; }
 
 // Register-staged kernel configurations: (NB, KB, waves, m-blocks, slices).  Nout = 512
 // runs 16 waves of 32 channels per 32-row range (64 weight VGPRs per lane: 4 waves
 // per SIMD, so one wave's latency hides behind another's work), as one 16-wave
-// workgroup or as two 8-wave slice workgroups (CTN_WS_S512); Nout = 256 runs 8 waves
+// workgroup (two 8-wave slice workgroups per CU are instantiated but not dispatched:
+// ws_slices); Nout = 256 runs 8 waves
 // of 32 channels with a 128-register weight slice on 16-row tiles.
 template <int OPK, int NK, int EPI>
 static hipError_t ws_launch_shape(const GemmRows& p, hipStream_t s) {
@@ -1050,7 +884,7 @@ static hipError_t ws_launch_nk(const GemmRows& p, hipStream_t s) {
 
 hipError_t launch_gemm_ws(const GemmRows& pa, hipStream_t s) {
   GemmRows p = pa;
-  p.err = device_error_word();   // the generation-word ring (CTN_WS_FLAGS) reports timeouts here
+  p.err = device_error_word();
   const int nk = p.aop.kind != OP_PLAIN ? p.aop.norm : p.norm;
   return nk == NORM_GLN ? ws_launch_nk<NORM_GLN>(p, s) : ws_launch_nk<NORM_CLN>(p, s);
 }

@@ -21,13 +21,6 @@
 
 namespace ctn {
 
-#ifndef CTN_DW_PF
-#define CTN_DW_PF 2
-#endif
-// dw_bwd, cLN: per-row statistics of 64 walk steps per lane, broadcast by v_readlane
-#ifndef CTN_DW_BATCH
-#define CTN_DW_BATCH 1
-#endif
 constexpr int DW_RPB = 128;   // rows per workgroup (element-wise kernels)
 constexpr int DW_MAXP = 8;
 constexpr int DW_MINSEG = 16; // shortest comb segment (halo rows cost (P-1)/seg)
@@ -35,7 +28,7 @@ constexpr int DW_WPS_FWD = 4, DW_WPS_BWD = 2;   // waves/SIMD the kernels' VGPR 
 // comb rows prefetched per lane: 2 for bf16 (the loop is latency-bound at one row
 // in flight: 8 waves x 48 B per lane per CU is half of what Little's law asks at
 // 6 TB/s), 1 for fp32 (parity mode; two would exceed the VGPR budgets above)
-template <typename T> constexpr int dw_pf() { return sizeof(T) == 2 ? CTN_DW_PF : 1; }
+template <typename T> constexpr int dw_pf() { return sizeof(T) == 2 ? 2 : 1; }
 
 // Segment length such that all work items of the launch are resident at once:
 // a wave owns 64/(H/8) items and walks its segment serially, so a second, partly
@@ -494,7 +487,7 @@ __global__ __launch_bounds__(256) void dw_bwd_kernel(DwArgs a) {
       fetch_g(j + D + GT, pd[q], pg[q], pok[q], prow[q]);
       fetch_h(j + D + AT, ph[q], pokh[q], prowh[q]);
     }
-    if constexpr (NK != NORM_GLN && CTN_DW_BATCH) {
+    if constexpr (NK != NORM_GLN) {   // per-row statistics of 64 walk steps per lane, broadcast by v_readlane
       if (wave_item) {
         if (j - bbase >= 64) batch_load(j);
         bstep = j;

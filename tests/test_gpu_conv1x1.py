@@ -43,8 +43,8 @@ the factor two of the second.
 Row geometries.  With K <= 128 the padded length is Kp = 128 and rows = 128 M: 4 M tiles
 of 32 rows, 8 M tiles of 16 rows.  A kernel's grid is min(tiles, cap) row ranges; range r
 takes tiles [tiles r / ranges, tiles (r + 1) / ranges).  Constants the table was built for
-(test_table_constants_match_the_source pins them): CTN_WS_GRID = 256, cap 80 =
-(256 / 3) / 8 * 8 for the three-slice 1536-channel form, CTN_WS_DR = 6 (the LDS-DMA ring of
+(test_table_constants_match_the_source pins them): WS_GRID = 256, cap 80 =
+(256 / 3) / 8 * 8 for the three-slice 1536-channel form, WS_DR = 6 (the LDS-DMA ring of
 the 16-wave forms: 5 tiles in flight in the prologue), 32-row tiles for 512 / 1536 outputs,
 16-row tiles and a two-accumulator software pipeline (tile parity) for 256 outputs.
 
@@ -76,7 +76,7 @@ K: 1 (with M = 1 only), then 97, 100, 127, 128: the padding boundary in the midd
 32-row tile, at row 4 of a tile, on a tile's last row, and absent.  M = 1 runs at all of
 them; the other M take them in turn (every M list meets every K).  Two Kp > 128 cases per
 weight-stationary shape, (M, K) = (5, 129) and (3, 300): ranges that straddle utterances
-and a padding band in the middle of a range.  A change to CTN_WS_GRID, CTN_WS_DR, the
+and a padding band in the middle of a range.  A change to WS_GRID, WS_DR, the
 tile rows or the slice counts moves the rows of this table: rebuild the M lists from them
 (M such that tiles = cap - 1 tile's worth, cap, cap + 1, and 5, 6, 6-7, 7 tiles per range).
 """
@@ -194,8 +194,8 @@ def tiles_per_range(rows, tile, cap):
 # ----------------------------------------------------------------------------
 def test_table_constants_match_the_source():
     src = open(os.path.join(ROOT, "conv-tasnet_amd", "csrc", "ctn_gemm_ws.hip")).read()
-    assert int(re.search(r"#define CTN_WS_GRID (\d+)", src).group(1)) == WS_GRID
-    assert int(re.search(r"#define CTN_WS_DR (\d+)", src).group(1)) == WS_DR
+    assert int(re.search(r"constexpr int WS_WAVES = 8, WS_TM = 16, WS_GRID = (\d+);", src).group(1)) == WS_GRID
+    assert int(re.search(r"constexpr int WS_DR = (\d+);", src).group(1)) == WS_DR
     assert (WS_GRID // 3) // 8 * 8 == WS_GRID_1536
     assert "(WS_GRID / 3) / 8 * 8" in src and "constexpr int WS_WAVES = 8, WS_TM = 16" in src
 

@@ -112,67 +112,6 @@ int main(int argc, char** argv) {
     }
   };
 
-#if CTN_DV_DBG & 8
-  {   // per-tile, per-lane epilogue sums and their inputs (stored to g.R by the kernel), run to run
-    const size_t nrec = (size_t)(rows / 32) * (H / 128) * 8 * 64;   // records of 12 words
-    void* dbg; CK(hipMalloc(&dbg, nrec * 48));
-    g.R = dbg;
-    const auto hd = get<uint16_t>(d, cn);
-    std::vector<uint32_t> first;
-    const char* fld[12] = {"s", "q", "alpha", "-", "r0.x", "r0.y", "r1.x", "r1.y", "e0.m", "e0.r", "e1.m", "e1.r"};
-    for (int r = 0; r < NRUN; ++r) {
-      CK(hipMemset(dbg, 0, nrec * 48));
-      launch_once(true, nullptr);
-      auto v = get<uint32_t>(dbg, nrec * 12);
-      if (r == 0) { first = v; continue; }
-      long nf[12] = {0};
-      long shown = 0;
-      for (size_t i = 0; i < v.size(); ++i)
-        if (v[i] != first[i]) {
-          ++nf[i % 12];
-          const size_t rec = i / 12;
-          const long lane = rec % 64, w = rec / 64 % 8, sl = rec / 512 % 4, t = rec / 2048;
-          if (shown++ < 4)
-            printf("   tile %ld slice %ld wave %ld lane %ld field %s: 0x%08x vs 0x%08x\n", t, sl, w, lane, fld[i % 12],
-                   v[i], first[i]);
-        }
-      printf("run %d differing fields:", r);
-      for (int f = 0; f < 12; ++f) printf(" %s=%ld", fld[f], nf[f]);
-      printf("\n");
-      // the r values against d itself: lane (lg, lr) of wave w reads row lr / 16+lr, channels
-      // n0 + 32*(w/2) + 8*lg + 4*(w&1) .. +3
-      long bad = 0;
-      for (size_t rec = 0; rec < nrec; ++rec) {
-        const long lane = rec % 64, w = rec / 64 % 8, sl = rec / 512 % 4, t = rec / 2048;
-        const long ch = sl * 128 + 32 * (w / 2) + 8 * (lane >> 4) + 4 * (w & 1);
-        for (int j = 0; j < 2; ++j) {
-          const long row = t * 32 + 16 * j + (lane & 15);
-          const uint32_t lo = hd[row * H + ch] | ((uint32_t)hd[row * H + ch + 1] << 16);
-          const uint32_t hi = hd[row * H + ch + 2] | ((uint32_t)hd[row * H + ch + 3] << 16);
-          bad += v[rec * 12 + 4 + 2 * j] != lo;
-          bad += v[rec * 12 + 5 + 2 * j] != hi;
-        }
-      }
-      printf("   r values off d: %ld\n", bad);
-    }
-    return 0;
-  }
-#endif
-#if CTN_DV_DBG & 16
-  {   // the consumers' R-image reads, stored in place of C: every value must be d's
-    const auto hd = get<uint16_t>(d, cn);
-    for (int r = 0; r < NRUN; ++r) {
-      Out o;
-      launch_once(true, &o);
-      long n = 0, first = -1;
-      for (long i = 0; i < cn; ++i)
-        if (o.c[i] != hd[i]) { if (first < 0) first = i; ++n; }
-      printf("R-image readback run %d: %ld of %ld values differ from d (first row %ld col %ld)\n", r, n, cn,
-             first < 0 ? -1 : first / H, first < 0 ? -1 : first % H);
-    }
-    return 0;
-  }
-#endif
   Out ref, cur;
   launch_once(false, &ref);
   launch_once(true, &cur);
@@ -263,7 +202,7 @@ int main(int argc, char** argv) {
       CK(hipEventSynchronize(e1));
       float ms; CK(hipEventElapsedTime(&ms, e0, e1));
       const double us = ms * 1e3 / NIT, cb = rows * (B + H) * 2.0;
-      printf("COLS CJC=%d M=%d K=%d %8.1f us  %7.0f GB/s (alg. bytes, %d ranges)\n", CTN_DV_CJC, M, K, us, cb / us * 1e-3,
+      printf("COLS CJC=%d M=%d K=%d %8.1f us  %7.0f GB/s (alg. bytes, %d ranges)\n", DV_CJC, M, K, us, cb / us * 1e-3,
              c.nchunks);
     }
   }
