@@ -23,6 +23,10 @@ Parity with mir_eval is UNPINNED (mir_eval is not installed and no fixture of
 its output exists in the reference); tests/test_pipeline.py checks the
 metric's defining properties instead (exact estimates, filtered estimates,
 additive noise at a known SNR, permutation recovery).
+
+``bss_criteria_device`` / ``bss_eval_sources_batch`` (below) run the same decomposition
+for a padded batch on the device (csrc/ctn_bss.hip); the functions above
+stay the host restatement they are tested against (tests/test_gpu_bss_eval.py).
 """
 from __future__ import annotations
 
@@ -112,3 +116,119 @@ def bss_eval_sources(reference_sources, estimated_sources, compute_permutation=T
     best = perms[int(np.argmax([np.mean(sir[list(p), dum]) for p in perms]))]
     idx = (list(best), dum)
     return sdr[idx], sir[idx], sar[idx], np.asarray(best)
+
+
+# ----------------------------------------------------------------------------
+# Device path (csrc/ctn_bss.hip through ctn_bss_eval): the same decomposition for a ragged
+# batch, direct-form fp64 lag correlations and one Cholesky factorisation per
+# (utterance, system) instead of FFT correlations and one LU solve per (estimate, reference).
+# ----------------------------------------------------------------------------
+WS_LIMIT = 1 << 30          # bytes of library workspace per call; larger batches are split
+
+
+def _lengths_tensor(lengths, M, T, device):
+    import torch
+    if lengths is None:
+        return torch.full((M,), T, dtype=torch.int32, device=device)
+    lengths = torch.as_tensor(lengths).to(device=device, dtype=torch.int32).reshape(-1)
+    if lengths.numel() != M:
+        raise ValueError(f"{lengths.numel()} lengths for {M} utterances")
+    return lengths.contiguous()
+
+
+def bss_criteria_device(refs, sigs, lengths=None, flen=FLEN):
+    """refs [M, C, T], sigs [M, E, T] (device tensors; utterance m uses its first lengths[m]
+    samples, the rest is never read) -> (sdr, sir, sar), each [M, E, C] fp64 on the device:
+    the criteria of signal e against reference j, and status [M] (1: a Gram matrix of the
+    utterance was numerically rank-deficient, its row is meaningless)."""
+    import ctypes
+
+    import torch
+
+    import ctn_lib as L
+    L.require_device(refs, "bss_criteria_device")
+    L.require_device(sigs, "bss_criteria_device")
+    if refs.dim() != 3 or sigs.dim() != 3 or refs.shape[0] != sigs.shape[0] or refs.shape[2] != sigs.shape[2]:
+        raise ValueError(f"shape mismatch: references {tuple(refs.shape)}, signals {tuple(sigs.shape)}")
+    refs, sigs = refs.float().contiguous(), sigs.float().contiguous()
+    (M, C, T), E = refs.shape, sigs.shape[1]
+    lengths = _lengths_tensor(lengths, M, T, refs.device)
+    lib = L.load()
+    energies = torch.empty(M, E, C, 5, dtype=torch.float64, device=refs.device)
+    status = torch.empty(M, dtype=torch.int32, device=refs.device)
+    one = lib.ctn_bss_workspace_bytes(ctypes.byref(L.BssDesc(1, C, E, T, flen)))
+    if one == 0:                  # unsupported shape: let the entry point name the reason
+        L.check(lib.ctn_bss_eval(ctypes.byref(L.BssDesc(1, C, E, T, flen)), None, None, None, None, None, None, 0,
+                                 None), "ctn_bss_eval")
+    step = max(1, min(M, WS_LIMIT // one, 65535))
+    ws = L.workspace(lib.ctn_bss_workspace_bytes(ctypes.byref(L.BssDesc(step, C, E, T, flen))), refs.device)
+    for m0 in range(0, M, step):
+        m1 = min(M, m0 + step)
+        d = L.BssDesc(m1 - m0, C, E, T, flen)
+        L.check(lib.ctn_bss_eval(ctypes.byref(d), L.ptr(refs[m0:m1]), L.ptr(sigs[m0:m1]), L.ptr(lengths[m0:m1]),
+                                 L.ptr(energies[m0:m1]), L.ptr(status[m0:m1]), L.ptr(ws), ws.numel(),
+                                 L.stream_handle(refs.device)), "ctn_bss_eval")
+    inf = torch.full_like(energies[..., 0], float("inf"))
+
+    def db(num, den):             # _db: a zero denominator gives +inf
+        return torch.where(den == 0, inf, 10.0 * torch.log10(num / den))
+    v = energies.unbind(-1)
+    return db(v[0], v[2]), db(v[0], v[1]), db(v[3], v[4]), status
+
+
+def _check_batch(refs, ests, lengths, flen):
+    """The ValueErrors of bss_eval_sources for a padded batch -> lengths as a list."""
+    import torch
+    if refs.dim() != 3 or refs.shape != ests.shape:
+        raise ValueError(f"shape mismatch: references {tuple(refs.shape)}, estimates {tuple(ests.shape)}")
+    M, C, T = refs.shape
+    lengths = _lengths_tensor(lengths, M, T, refs.device)
+    n = lengths.tolist()
+    if max(n) > T or min(n) < flen:
+        bad = min(n) if min(n) < flen else max(n)
+        raise ValueError(f"signals of {bad} samples are shorter than the {flen}-tap filters" if bad < flen else
+                         f"length {bad} exceeds the {T} samples of the batch")
+    inside = torch.arange(T, device=refs.device).unsqueeze(0) < lengths.unsqueeze(1)          # [M, T]
+    if not bool(((refs != 0) & inside.unsqueeze(1)).any(-1).all()):
+        raise ValueError("a reference source is all zeros (undefined SDR)")
+    return lengths, n
+
+
+def _assign(sdr, sir, sar, compute_permutation):
+    """[E >= C, C] criteria of one utterance (row e: estimate e) -> bss_eval_sources' result."""
+    n = sdr.shape[1]
+    dum = np.arange(n)
+    best = tuple(range(n))
+    if compute_permutation:
+        perms = list(itertools.permutations(range(n)))
+        best = perms[int(np.argmax([np.mean(sir[list(p), dum]) for p in perms]))]
+    idx = (list(best), dum)
+    return sdr[idx], sir[idx], sar[idx], np.asarray(best)
+
+
+def _on_host(status, n, C, flen):
+    """Utterances scored by the host routine: flagged by the library, or with fewer samples
+    than unknowns (lengths + flen - 1 < C * flen: the Gram matrix is rank-deficient by
+    construction and the host's solve / lstsq decides the result)."""
+    return [bool(status[m]) or n[m] + flen - 1 < C * flen for m in range(len(n))]
+
+
+def bss_eval_sources_batch(reference_sources, estimated_sources, lengths=None, compute_permutation=True, flen=FLEN):
+    """bss_eval_sources of every utterance of a padded batch, computed on the device:
+    reference_sources, estimated_sources [M, C, T] device tensors, lengths [M] (None: T)
+    -> (sdr, sir, sar, perm), numpy arrays [M, C]; row m is bss_eval_sources(refs[m, :,
+    :lengths[m]], ests[m, :, :lengths[m]], compute_permutation, flen)."""
+    refs, ests = reference_sources, estimated_sources
+    lengths, n = _check_batch(refs, ests, lengths, flen)
+    M, C, _ = refs.shape
+    sdr, sir, sar, status = (t.cpu().numpy() for t in bss_criteria_device(refs, ests, lengths, flen))
+    out = [np.empty((M, C)) for _ in range(3)] + [np.empty((M, C), dtype=np.int64)]
+    for m, host in enumerate(_on_host(status, n, C, flen)):
+        if host:
+            res = bss_eval_sources(refs[m, :, :n[m]].double().cpu().numpy(), ests[m, :, :n[m]].double().cpu().numpy(),
+                                   compute_permutation, flen)
+        else:
+            res = _assign(sdr[m], sir[m], sar[m], compute_permutation)
+        for o, r in zip(out, res):
+            o[m] = r
+    return tuple(out)

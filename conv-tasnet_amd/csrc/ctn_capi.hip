@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/ctn.h"
+#include "ctn_bss.h"
 #include "ctn_common.h"
 #include "ctn_kernels.h"
 
@@ -1535,6 +1536,41 @@ extern "C" int ctn_pit_backward(const ctn_pit_desc* d, const float* source, cons
   a.src = source; a.est = est; a.lengths = lengths; a.coef = const_cast<float*>(coef);
   a.g_loss = g_loss; a.g_maxsnr = g_max_snr; a.gest = g_est;
   CTN_HIP(launch_pit_backward(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+// ===========================================================================
+// BSS Eval v3 energies, ctn_bss.hip
+// ===========================================================================
+static int bss_check(const ctn_bss_desc* d) {
+  if (!d) return fail(CTN_ERR_ARG, "null descriptor");
+  if (d->M < 1 || d->C < 1 || d->E < 1 || d->flen < 1)
+    return fail(CTN_ERR_ARG, "bad BSS descriptor M=%d C=%d E=%d flen=%d (all >= 1)", d->M, d->C, d->E, d->flen);
+  if (d->T < d->flen) return fail(CTN_ERR_ARG, "T=%d samples are shorter than the %d-tap filters", d->T, d->flen);
+  if ((long)d->C * d->flen > BSS_MAX_ORDER)
+    return fail(CTN_ERR_UNSUPPORTED, "C*flen = %ld > %d (largest normal-equation system)", (long)d->C * d->flen,
+                BSS_MAX_ORDER);
+  if (d->M > BSS_MAX_M || d->E > BSS_MAX_M)
+    return fail(CTN_ERR_UNSUPPORTED, "M=%d E=%d: at most %d each per call", d->M, d->E, BSS_MAX_M);
+  return CTN_OK;
+}
+
+extern "C" size_t ctn_bss_workspace_bytes(const ctn_bss_desc* d) {
+  if (bss_check(d) != CTN_OK) return 0;
+  return bss_layout(d->M, d->C, d->E, d->T, d->flen).bytes;
+}
+
+extern "C" int ctn_bss_eval(const ctn_bss_desc* d, const float* refs, const float* sigs, const int32_t* lengths,
+                            double* energies, int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = bss_check(d)) return rc;
+  if (!refs || !sigs || !lengths || !energies || !status) return fail(CTN_ERR_ARG, "null pointer");
+  BssArgs a{};
+  a.M = d->M; a.C = d->C; a.E = d->E; a.T = d->T; a.flen = d->flen;
+  a.L = bss_layout(d->M, d->C, d->E, d->T, d->flen);
+  if (!ws || ws_bytes < a.L.bytes) return fail(CTN_ERR_WORKSPACE, "workspace %zu < %zu", ws_bytes, a.L.bytes);
+  a.refs = refs; a.sigs = sigs; a.lengths = lengths; a.energies = energies; a.status = status;
+  a.ws = reinterpret_cast<double*>(ws);
+  CTN_HIP(launch_bss_eval(a, (hipStream_t)stream));
   return CTN_OK;
 }
 

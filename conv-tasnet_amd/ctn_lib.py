@@ -14,7 +14,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CTN_HIP_LIB", os.path.join(_HERE, "libctn_hip.so"))
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 NORM_GLN, NORM_CLN, NORM_BN = 0, 1, 2
@@ -66,6 +66,11 @@ class CodecDesc(ctypes.Structure):
 
 class PitDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("M", "C", "T")]
+
+
+class BssDesc(ctypes.Structure):
+    """ctn_bss_desc (include/ctn.h, ABI v13); T is the row stride in samples."""
+    _fields_ = [(n, c_int32) for n in ("M", "C", "E", "T", "flen")]
 
 
 MASK_IDENTITY = 2
@@ -137,6 +142,8 @@ _SIGS = {
     "ctn_pit_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_pit_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "ctn_pit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p]),
+    "ctn_bss_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_bss_eval": (ctypes.c_int, [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
     "ctn_pack_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "ctn_opt_plan": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int]),
     "ctn_grad_clip_norm": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_float, c_void_p, c_void_p,

@@ -17,7 +17,10 @@ Same flags and printout as the reference.  Differences, each deliberate:
 * SDRi uses mir_eval's bss_eval_sources (evaluate.py:10,90-105) when it is
   importable and otherwise ``bss_eval.bss_eval_sources``, a from-scratch
   restatement of the same BSS Eval v3 algorithm (mir_eval is not installed in
-  this image, so SDRi parity is unpinned).
+  this image, so SDRi parity is unpinned, DESIGN.md §4);
+* ``--sdr_device 1`` (default 0: nothing changes) computes SDRi of a whole minibatch on
+  the device with that restatement's algorithm (``cal_SDRi_batch``, csrc/ctn_bss.hip,
+  DESIGN.md §18) instead of once per utterance on the host; same printout.
 """
 import argparse
 
@@ -46,6 +49,8 @@ parser.add_argument('--num_workers', default=2, type=int,
                     help='DataLoader workers reading the wavs (the reference uses 2)')
 parser.add_argument('--pit_fix', default=0, type=int,
                     help='1: pair targets with the inverse of the best permutation (C >= 3)')
+parser.add_argument('--sdr_device', default=0, type=int,
+                    help='1: with --cal_sdr 1, compute SDRi on the device (bss_eval, batched HIP kernels)')
 
 
 def reorder_inverse(est, source, lengths):
@@ -61,7 +66,8 @@ class Evaluator:
     """Scores a trained model over one manifest directory (src/evaluate.py:33-90 behaviour:
     the same per-utterance printout and averages).  Minibatches are separated on the
     device, scored there in fp64 (SI-SNRi, cal_SISNRi_batch) and, with --cal_sdr, on the
-    host (SDRi, cal_SDRi); ``records`` keeps one (SI-SNRi, SDRi or None) per utterance."""
+    host (SDRi, cal_SDRi) or with --sdr_device on the device (cal_SDRi_batch); ``records``
+    keeps one (SI-SNRi, SDRi or None) per utterance."""
 
     def __init__(self, args):
         self.args = args
@@ -83,7 +89,9 @@ class Evaluator:
     def _score(self, mixture, lengths, source, paired):
         sisnri = cal_SISNRi_batch(source, paired, mixture, lengths).cpu().tolist()
         sdri = [None] * len(sisnri)
-        if self.args.cal_sdr:
+        if self.args.cal_sdr and getattr(self.args, 'sdr_device', 0):
+            sdri = cal_SDRi_batch(source, paired, mixture, lengths).tolist()
+        elif self.args.cal_sdr:
             mix_u, src_u, est_u = (remove_pad(t, lengths) for t in (mixture, source, paired))
             sdri = [cal_SDRi(src_u[b], est_u[b], mix_u[b]) for b in range(len(sisnri))]
         return list(zip(sisnri, sdri))
@@ -121,6 +129,29 @@ def cal_SDRi(src_ref, src_est, mix):
     sdr, sir, sar, popt = bss_eval_sources(src_ref, src_est)
     sdr0, sir0, sar0, popt0 = bss_eval_sources(src_ref, src_anchor)
     return float(np.mean(sdr - sdr0))
+
+
+def cal_SDRi_batch(source, estimate, mixture, lengths, flen=None):
+    """cal_SDRi of every utterance of a padded batch with bss_eval's device path: source /
+    estimate [B, C, T], mixture [B, T], lengths [B] -> numpy [B].  One library call scores
+    E = C + 1 signals per utterance, the C estimates and the mixture (the anchor's SDR
+    against reference j is the same for every permutation of C copies of the mixture)."""
+    import bss_eval
+    flen = bss_eval.FLEN if flen is None else flen
+    lengths, n = bss_eval._check_batch(source, estimate, lengths, flen)
+    B, C, T = source.shape
+    sigs = torch.cat((estimate, mixture.reshape(B, 1, T).to(estimate.dtype)), dim=1)
+    sdr, sir, sar, status = (t.cpu().numpy() for t in bss_eval.bss_criteria_device(source, sigs, lengths, flen))
+    out = np.empty(B)
+    for b, host in enumerate(bss_eval._on_host(status, n, C, flen)):
+        if host:
+            src_u, est_u = (t[b, :, :n[b]].double().cpu().numpy() for t in (source, estimate))
+            anchor = np.stack([mixture[b, :n[b]].double().cpu().numpy()] * C, axis=0)
+            out[b] = np.mean(bss_eval.bss_eval_sources(src_u, est_u, flen=flen)[0] -
+                             bss_eval.bss_eval_sources(src_u, anchor, flen=flen)[0])
+        else:
+            out[b] = np.mean(bss_eval._assign(sdr[b, :C], sir[b, :C], sar[b, :C], True)[0] - sdr[b, C])
+    return out
 
 
 def cal_SISNRi(src_ref, src_est, mix):

@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define CTN_ABI_VERSION 12
+#define CTN_ABI_VERSION 13
 
 typedef enum { CTN_DTYPE_F32 = 0, CTN_DTYPE_BF16 = 1 } ctn_dtype;
 /* CTN_NORM_BN: torch.nn.BatchNorm1d, chose_norm's fallback branch (conv_tasnet.py:302-303) */
@@ -221,6 +221,29 @@ int ctn_pit_forward(const ctn_pit_desc* d, const float* source, float* est, cons
                     void* stream);
 int ctn_pit_backward(const ctn_pit_desc* d, const float* source, const float* est, const int64_t* lengths,
                      const float* coef, const float* g_loss, const float* g_max_snr, float* g_est, void* stream);
+
+/* -------------------------------------------------------------------------
+ * BSS Eval v3 source metrics (ABI v13): the energies behind the SDR / SIR / SAR of
+ * mir_eval.separation.bss_eval_sources, which src/evaluate.py:90-105 calls on the host
+ * once per utterance.  For M utterances, C references and E scored signals per utterance,
+ * each signal is decomposed against the references with `flen`-tap distortion filters
+ * (the normal equations of the lag correlations, factored once per utterance and system
+ * and solved for all E signals).  fp32 inputs with row stride T samples; utterance m uses
+ * its first lengths[m] samples and never reads the rest (it may hold NaN).  All arithmetic
+ * is fp64 in a fixed order: two calls on the same inputs give the same bits.
+ * energies[m][e][j] = { |s_true+e_spat|^2, |e_interf|^2, |e_interf+e_artif|^2,
+ *                       |s_true+e_spat+e_interf|^2, |e_artif|^2 } of signal e against
+ * reference j: SDR = 10 log10(v0/v2), SIR = 10 log10(v0/v1), SAR = 10 log10(v3/v4).
+ * status[m] = 1 when a Cholesky pivot of one of utterance m's systems was not finite or
+ * <= order * 2^-52 * (largest diagonal entry) (rank-deficient references: its energies are
+ * then meaningless), else 0.  Limits: C * flen <= 4096, T >= flen, M and E <= 65535
+ * (0 workspace bytes / an error code beyond).
+ * ------------------------------------------------------------------------- */
+typedef struct { int32_t M, C, E, T, flen; } ctn_bss_desc;   /* T = row stride in samples */
+size_t ctn_bss_workspace_bytes(const ctn_bss_desc* d);
+int ctn_bss_eval(const ctn_bss_desc* d, const float* refs /*[M][C][T]*/, const float* sigs /*[M][E][T]*/,
+                 const int32_t* lengths /*[M]*/, double* energies /*[M][E][C][5]*/, int32_t* status /*[M]*/,
+                 void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
  * Parameter update: replaces torch.nn.utils.clip_grad_norm_(params, max_norm)
