@@ -15,6 +15,7 @@
 #include "../../include/ctn.h"
 #include "ctn_bss.h"
 #include "ctn_common.h"
+#include "ctn_dmix.h"
 #include "ctn_kernels.h"
 
 using namespace ctn;
@@ -1571,6 +1572,74 @@ extern "C" int ctn_bss_eval(const ctn_bss_desc* d, const float* refs, const floa
   a.refs = refs; a.sigs = sigs; a.lengths = lengths; a.energies = energies; a.status = status;
   a.ws = reinterpret_cast<double*>(ws);
   CTN_HIP(launch_bss_eval(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+// ===========================================================================
+// Dynamic mixing (draw + mix), ctn_dmix.hip
+// ===========================================================================
+static_assert(sizeof(ctn_dmix_entry) == sizeof(DmixEntry), "plan entry layout");
+static_assert(sizeof(ctn_dmix_desc) == 56, "ctn_dmix_desc layout");
+
+static int dmix_check(const ctn_dmix_desc* d) {
+  if (!d) return fail(CTN_ERR_ARG, "null descriptor");
+  if (d->M < 1 || d->T < 1 || d->n_utts < 1 || d->n_elig < 1)
+    return fail(CTN_ERR_ARG, "bad dynamic-mix descriptor M=%d T=%d n_utts=%d n_elig=%d (all >= 1)", d->M, d->T,
+                d->n_utts, d->n_elig);
+  if (d->C < 1 || d->max_tries < 1) return fail(CTN_ERR_ARG, "bad dynamic-mix descriptor C=%d max_tries=%d", d->C, d->max_tries);
+  if ((d->pool_dtype != 0 && d->pool_dtype != 1) || (d->level_mode != 0 && d->level_mode != 1))
+    return fail(CTN_ERR_ARG, "pool_dtype=%d level_mode=%d: each 0 or 1", d->pool_dtype, d->level_mode);
+  if (!isfinite(d->level_lo_db) || !isfinite(d->level_hi_db) || !isfinite(d->peak) || d->peak < 0.f)
+    return fail(CTN_ERR_ARG, "levels and peak must be finite, peak >= 0");
+  if (d->C > DMIX_MAX_C) return fail(CTN_ERR_UNSUPPORTED, "C=%d > %d slots per row", d->C, DMIX_MAX_C);
+  if (d->max_tries > DMIX_MAX_TRIES)
+    return fail(CTN_ERR_UNSUPPORTED, "max_tries=%d > %d", d->max_tries, DMIX_MAX_TRIES);
+  if (d->T > (1 << 30)) return fail(CTN_ERR_UNSUPPORTED, "T=%d > 2^30 samples", d->T);
+  const long nchunk = ((long)d->T + DMIX_CHUNK - 1) / DMIX_CHUNK;
+  if ((long)d->M * d->C > INT32_MAX / nchunk)
+    return fail(CTN_ERR_UNSUPPORTED, "M*C*ceil(T/%d) = %ld*%ld workgroups exceed one grid", DMIX_CHUNK,
+                (long)d->M * d->C, nchunk);
+  return CTN_OK;
+}
+
+extern "C" size_t ctn_dmix_workspace_bytes(const ctn_dmix_desc* d) {
+  if (dmix_check(d) != CTN_OK) return 0;
+  return dmix_layout(d->M, d->C, d->T).bytes;
+}
+
+extern "C" int ctn_dmix_draw(const ctn_dmix_desc* d, const int64_t* off, const int32_t* spk, const int32_t* elig,
+                             int64_t first_sample, int64_t* first_sample_dev, int64_t advance, ctn_dmix_entry* plan,
+                             void* stream) {
+  if (int rc = dmix_check(d)) return rc;
+  if (!off || !spk || !elig || !plan) return fail(CTN_ERR_ARG, "null pointer");
+  DmixDrawArgs a{};
+  a.M = d->M; a.C = d->C; a.T = d->T; a.U = d->n_utts; a.E = d->n_elig; a.max_tries = d->max_tries;
+  a.lo_db = d->level_lo_db; a.hi_db = d->level_hi_db;
+  a.seed_lo = (uint32_t)d->seed; a.seed_hi = (uint32_t)(d->seed >> 32);
+  a.off = off; a.spk = spk; a.elig = elig;
+  a.first = first_sample; a.first_dev = first_sample_dev; a.advance = advance;
+  a.plan = reinterpret_cast<DmixEntry*>(plan);
+  CTN_HIP(launch_dmix_draw(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+extern "C" int ctn_dmix_mix(const ctn_dmix_desc* d, const void* pool, const int64_t* off, const ctn_dmix_entry* plan,
+                            float* gains, float* sources, float* mixture, int32_t* status, void* ws, size_t ws_bytes,
+                            void* stream) {
+  if (int rc = dmix_check(d)) return rc;
+  if (!pool || !off || !plan || !gains || !sources || !mixture || !status) return fail(CTN_ERR_ARG, "null pointer");
+  if ((uintptr_t)pool % (d->pool_dtype == 0 ? 2 : 4) || (uintptr_t)sources % 4 || (uintptr_t)mixture % 4)
+    return fail(CTN_ERR_ARG, "pool, sources or mixture is not aligned to its element size");
+  DmixMixArgs a{};
+  a.M = d->M; a.C = d->C; a.T = d->T; a.U = d->n_utts; a.pool_dtype = d->pool_dtype; a.level_mode = d->level_mode;
+  a.peak = d->peak;
+  a.L = dmix_layout(d->M, d->C, d->T);
+  if (!ws || ws_bytes < a.L.bytes) return fail(CTN_ERR_WORKSPACE, "workspace %zu < %zu", ws_bytes, a.L.bytes);
+  if ((uintptr_t)ws % 8) return fail(CTN_ERR_ARG, "workspace is not 8-byte aligned");
+  a.pool = pool; a.off = off; a.plan = reinterpret_cast<const DmixEntry*>(plan);
+  a.gains = gains; a.sources = sources; a.mixture = mixture; a.status = status;
+  a.ws = reinterpret_cast<char*>(ws);
+  CTN_HIP(launch_dmix_mix(a, (hipStream_t)stream));
   return CTN_OK;
 }
 

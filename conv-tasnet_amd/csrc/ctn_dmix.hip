@@ -1,0 +1,303 @@
+// Dynamic mixing on the device (include/ctn.h: ctn_dmix_draw, ctn_dmix_mix).
+//
+// draw : one thread per batch row; Philox4x32-10 counter (g_lo, g_hi, slot, try), key = seed.
+// mix  : ssq   (level_mode 1) per-chunk sums of squares of every segment, fp64
+//        gain0 one thread per row: validity, status, gains before the guard
+//        peak  (peak > 0) per-chunk max |sum_c fl32(g_c x_c)| of every row
+//        write final gains, sources, mixture
+// A workgroup of 256 threads covers DMIX_CHUNK = 2048 consecutive samples of one segment
+// (ssq) or one row (peak, write), 8 per thread.  A segment starts at any sample of the pool,
+// so an int16 segment at any 2-byte and the fp32 rows (T is arbitrary) at any 4-byte
+// alignment: the 16-byte accesses are declared with that alignment (global memory on
+// gfx950 is accessed in unaligned mode) and cover exactly the thread's 8 samples, never a
+// byte outside the segment or the row; a last partial group of 8 goes sample by sample.
+// No atomics; every sum and max is finished in index order.  The exactness contract
+// (one rounding per source sample, the mixture an ordered fp32 sum of the stored sources)
+// needs every product and sum below to stay a separate operation:
+#pragma clang fp contract(off)
+
+#include "ctn_common.h"
+#include "ctn_dmix.h"
+
+namespace ctn {
+
+static_assert(sizeof(DmixEntry) == 16, "plan entry is 16 bytes");
+static_assert(DMIX_CHUNK == 256 * 8, "a workgroup covers one chunk");
+
+DmixLayout dmix_layout(int M, int C, int T) {
+  DmixLayout L{};
+  L.nchunk = (int)(((long)T + DMIX_CHUNK - 1) / DMIX_CHUNK);
+  const size_t mc = (size_t)M * C;
+  size_t o = 0;
+  L.off_ssq = o;  o += mc * L.nchunk * sizeof(double);
+  L.off_g0 = o;   o += (mc * sizeof(float) + 15) / 16 * 16;
+  L.off_pmax = o; o += ((size_t)M * L.nchunk * sizeof(float) + 15) / 16 * 16;
+  L.bytes = o;
+  return L;
+}
+
+// ---------------------------------------------------------------------------
+// draw
+// ---------------------------------------------------------------------------
+struct Philox { uint32_t r[4]; };
+CTN_DEV Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+    c1 = (uint32_t)p1;
+    c3 = (uint32_t)p0;
+    c0 = n0;
+    c2 = n2;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return Philox{{c0, c1, c2, c3}};
+}
+
+__global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
+  const int m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= a.M) return;
+  const uint64_t g = (uint64_t)((a.first_dev ? *a.first_dev : a.first) + m);
+  int32_t taken[DMIX_MAX_C];   // speakers of the accepted slots; bit q of `valid`: slot q has one
+  uint32_t valid = 0;
+  for (int c = 0; c < a.C; ++c) {
+    DmixEntry e{-1, 0, 0.f, 0};
+    int32_t sp = 0;
+    for (int j = 0; j < a.max_tries; ++j) {
+      const Philox r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)c, (uint32_t)j, a.seed_lo, a.seed_hi);
+      const int32_t utt = a.elig[((uint64_t)r.r[0] * (uint64_t)a.E) >> 32];
+      const float u = (float)(r.r[2] >> 8) * 0x1p-24f;
+      e.level_db = a.lo_db + (a.hi_db - a.lo_db) * u;
+      e.tries = j + 1;
+      e.utt = -1;
+      e.start = 0;
+      if (utt < 0 || utt >= a.U) break;                    // a bad table entry: flagged by the mix
+      const int64_t n = a.off[utt + 1] - a.off[utt] - a.T + 1;
+      if (n < 1 || n > 0x7fffffffLL) break;
+      e.utt = utt;
+      e.start = (int32_t)(((uint64_t)r.r[1] * (uint64_t)n) >> 32);
+      sp = a.spk[utt];
+      bool clash = false;
+      for (int q = 0; q < c; ++q) clash = clash || (((valid >> q) & 1u) && taken[q] == sp);
+      if (!clash) break;
+    }
+    taken[c] = sp;
+    if (e.utt >= 0) valid |= 1u << c;
+    a.plan[(size_t)m * a.C + c] = e;
+  }
+}
+
+__global__ void dmix_advance_kernel(int64_t* first, int64_t advance) { *first += advance; }
+
+hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s) {
+  dmix_draw_kernel<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+  if (a.first_dev) dmix_advance_kernel<<<dim3(1), dim3(1), 0, s>>>(a.first_dev, a.advance);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// mix
+// ---------------------------------------------------------------------------
+typedef uint32_t v4u_a2 __attribute__((ext_vector_type(4), aligned(2)));
+typedef float v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));
+
+// First pool sample of the entry's segment, or -1 for an entry that must not be read.
+CTN_DEV int64_t seg_base(const DmixMixArgs& a, const DmixEntry& e) {
+  if (e.utt < 0 || e.utt >= a.U || e.start < 0) return -1;
+  const int64_t o = a.off[e.utt], len = a.off[e.utt + 1] - o;
+  if ((int64_t)e.start + a.T > len) return -1;
+  return o + e.start;
+}
+
+// Samples [t0, t0 + 8) of the segment at pool sample `base` (exact in fp32); zeros past T.
+template <int DT> CTN_DEV void load8(const void* pool, int64_t base, int t0, int T, float x[8]) {
+  if (t0 + 8 <= T) {
+    if constexpr (DT == 0) {
+      const v4u_a2 v = *reinterpret_cast<const v4u_a2*>(reinterpret_cast<const int16_t*>(pool) + base + t0);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x[2 * i] = (float)(int16_t)(v[i] & 0xffffu) * 0x1p-15f;
+        x[2 * i + 1] = (float)(int16_t)(v[i] >> 16) * 0x1p-15f;
+      }
+    } else {
+      const float* p = reinterpret_cast<const float*>(pool) + base + t0;
+      const v4f_a4 lo = *reinterpret_cast<const v4f_a4*>(p), hi = *reinterpret_cast<const v4f_a4*>(p + 4);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        x[i] = lo[i];
+        x[4 + i] = hi[i];
+      }
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      x[i] = 0.f;
+      if (t0 + i < T) {
+        if constexpr (DT == 0) x[i] = (float)reinterpret_cast<const int16_t*>(pool)[base + t0 + i] * 0x1p-15f;
+        else x[i] = reinterpret_cast<const float*>(pool)[base + t0 + i];
+      }
+    }
+  }
+}
+
+CTN_DEV void store8(float* row, int t0, int T, const float v[8]) {
+  if (t0 + 8 <= T) {
+    *reinterpret_cast<v4f_a4*>(row + t0) = v4f_a4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<v4f_a4*>(row + t0 + 4) = v4f_a4{v[4], v[5], v[6], v[7]};
+  } else {
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+      if (t0 + i < T) row[t0 + i] = v[i];
+  }
+}
+
+// Block-wide fp32 max (a max has no rounding: any order gives the same bits); valid in thread 0.
+CTN_DEV float block_max(float v, float* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) v = fmaxf(v, red[w]);
+  return v;
+}
+
+// grid: (m*C + c) * nchunk + chunk
+template <int DT> __global__ __launch_bounds__(256) void dmix_ssq_kernel(DmixMixArgs a) {
+  __shared__ double red[4];
+  const int nchunk = a.L.nchunk;
+  const int mc = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
+  double* out = reinterpret_cast<double*>(a.ws + a.L.off_ssq) + (size_t)mc * nchunk + chunk;
+  const int64_t base = seg_base(a, a.plan[mc]);
+  if (base < 0) {
+    if (threadIdx.x == 0) *out = 0.0;
+    return;
+  }
+  float x[8];
+  load8<DT>(a.pool, base, chunk * DMIX_CHUNK + (int)threadIdx.x * 8, a.T, x);
+  double s[1] = {0.0};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s[0] += (double)x[i] * (double)x[i];
+  block_sum_d<1>(s, red);
+  if (threadIdx.x == 0) *out = s[0];
+}
+
+__global__ __launch_bounds__(64) void dmix_gain0_kernel(DmixMixArgs a) {
+  const int m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= a.M) return;
+  bool ok = true;
+  for (int c = 0; c < a.C; ++c) ok = ok && seg_base(a, a.plan[(size_t)m * a.C + c]) >= 0;
+  a.status[m] = ok ? 0 : 1;
+  float* g0 = reinterpret_cast<float*>(a.ws + a.L.off_g0) + (size_t)m * a.C;
+  const double* ssq = reinterpret_cast<const double*>(a.ws + a.L.off_ssq);
+  for (int c = 0; c < a.C; ++c) {
+    if (!ok) {
+      g0[c] = 0.f;
+      continue;
+    }
+    double g = exp10((double)a.plan[(size_t)m * a.C + c].level_db / 20.0);
+    if (a.level_mode == 1) {
+      double s = 0.0;
+      for (int k = 0; k < a.L.nchunk; ++k) s += ssq[((size_t)m * a.C + c) * a.L.nchunk + k];
+      g /= fmax(sqrt(s / (double)a.T), 1e-4);
+    }
+    g0[c] = (float)g;
+  }
+}
+
+// The row's unguarded mixture samples [t0, t0 + 8): the arithmetic of the final write.
+template <int DT> CTN_DEV void mix8(const DmixMixArgs& a, const int64_t* base, const float* g, int t0, float acc[8],
+                                    float* sources_row0) {
+  for (int c = 0; c < a.C; ++c) {
+    float x[8], v[8];
+    load8<DT>(a.pool, base[c], t0, a.T, x);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      v[i] = g[c] * x[i];
+      acc[i] = c == 0 ? v[i] : acc[i] + v[i];
+    }
+    if (sources_row0) store8(sources_row0 + (size_t)c * a.T, t0, a.T, v);
+  }
+}
+
+// grid: m * nchunk + chunk
+template <int DT> __global__ __launch_bounds__(256) void dmix_peak_kernel(DmixMixArgs a) {
+  __shared__ float red[4];
+  __shared__ int64_t base[DMIX_MAX_C];
+  __shared__ float g[DMIX_MAX_C];
+  const int nchunk = a.L.nchunk;
+  const int m = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
+  float* out = reinterpret_cast<float*>(a.ws + a.L.off_pmax) + (size_t)m * nchunk + chunk;
+  if (a.status[m] != 0) {
+    if (threadIdx.x == 0) *out = 0.f;
+    return;
+  }
+  if ((int)threadIdx.x < a.C) {
+    base[threadIdx.x] = seg_base(a, a.plan[(size_t)m * a.C + threadIdx.x]);
+    g[threadIdx.x] = reinterpret_cast<const float*>(a.ws + a.L.off_g0)[(size_t)m * a.C + threadIdx.x];
+  }
+  __syncthreads();
+  float acc[8];
+  mix8<DT>(a, base, g, chunk * DMIX_CHUNK + (int)threadIdx.x * 8, acc, nullptr);
+  float p = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) p = fmaxf(p, fabsf(acc[i]));   // samples past T are zeros
+  p = block_max(p, red);
+  if (threadIdx.x == 0) *out = p;
+}
+
+// grid: m * nchunk + chunk
+template <int DT> __global__ __launch_bounds__(256) void dmix_write_kernel(DmixMixArgs a) {
+  __shared__ int64_t base[DMIX_MAX_C];
+  __shared__ float g[DMIX_MAX_C];
+  const int nchunk = a.L.nchunk;
+  const int m = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
+  const int t0 = chunk * DMIX_CHUNK + (int)threadIdx.x * 8;
+  float* src0 = a.sources + (size_t)m * a.C * a.T;
+  float* mixrow = a.mixture + (size_t)m * a.T;
+  if (a.status[m] != 0) {
+    const float z[8] = {};
+    for (int c = 0; c < a.C; ++c) store8(src0 + (size_t)c * a.T, t0, a.T, z);
+    store8(mixrow, t0, a.T, z);
+    if (chunk == 0 && (int)threadIdx.x < a.C) a.gains[(size_t)m * a.C + threadIdx.x] = 0.f;
+    return;
+  }
+  if ((int)threadIdx.x < a.C) {
+    const int c = threadIdx.x;
+    base[c] = seg_base(a, a.plan[(size_t)m * a.C + c]);
+    float gc = reinterpret_cast<const float*>(a.ws + a.L.off_g0)[(size_t)m * a.C + c];
+    if (a.peak > 0.f) {
+      const float* pm = reinterpret_cast<const float*>(a.ws + a.L.off_pmax) + (size_t)m * nchunk;
+      float p = 0.f;
+      for (int k = 0; k < nchunk; ++k) p = fmaxf(p, pm[k]);
+      if (p > a.peak) gc = gc * (a.peak / p);
+    }
+    g[c] = gc;
+    if (chunk == 0) a.gains[(size_t)m * a.C + c] = gc;
+  }
+  __syncthreads();
+  float acc[8];
+  mix8<DT>(a, base, g, t0, acc, src0);
+  store8(mixrow, t0, a.T, acc);
+}
+
+hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s) {
+  const int nchunk = a.L.nchunk;
+  const dim3 blk(256), rows((unsigned)((long)a.M * nchunk)), segs((unsigned)((long)a.M * a.C * nchunk));
+  const bool i16 = a.pool_dtype == 0;
+  if (a.level_mode == 1) {
+    if (i16) dmix_ssq_kernel<0><<<segs, blk, 0, s>>>(a);
+    else dmix_ssq_kernel<1><<<segs, blk, 0, s>>>(a);
+  }
+  dmix_gain0_kernel<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+  if (a.peak > 0.f) {
+    if (i16) dmix_peak_kernel<0><<<rows, blk, 0, s>>>(a);
+    else dmix_peak_kernel<1><<<rows, blk, 0, s>>>(a);
+  }
+  if (i16) dmix_write_kernel<0><<<rows, blk, 0, s>>>(a);
+  else dmix_write_kernel<1><<<rows, blk, 0, s>>>(a);
+  return hipGetLastError();
+}
+
+}  // namespace ctn

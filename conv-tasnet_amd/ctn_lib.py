@@ -73,6 +73,17 @@ class BssDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("M", "C", "E", "T", "flen")]
 
 
+class DmixDesc(ctypes.Structure):
+    """ctn_dmix_desc (include/ctn.h): dynamic mixing on the device."""
+    _fields_ = ([(n, c_int32) for n in ("M", "C", "T", "n_utts", "n_elig", "pool_dtype", "level_mode", "max_tries")] +
+                [(n, ctypes.c_float) for n in ("level_lo_db", "level_hi_db", "peak")] + [("seed", ctypes.c_uint64)])
+
+
+class DmixEntry(ctypes.Structure):
+    """ctn_dmix_entry: one slot of a mixing plan."""
+    _fields_ = [("utt", c_int32), ("start", c_int32), ("level_db", ctypes.c_float), ("tries", c_int32)]
+
+
 MASK_IDENTITY = 2
 
 
@@ -144,6 +155,9 @@ _SIGS = {
     "ctn_pit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p]),
     "ctn_bss_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_bss_eval": (ctypes.c_int, [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_dmix_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_dmix_draw": (ctypes.c_int, [c_void_p] * 4 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
+    "ctn_dmix_mix": (ctypes.c_int, [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "ctn_pack_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "ctn_opt_plan": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int]),
     "ctn_grad_clip_norm": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_float, c_void_p, c_void_p,

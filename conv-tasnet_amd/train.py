@@ -16,7 +16,10 @@ Differences, each deliberate:
 * ``--shuffle`` reshuffles the minibatch order per epoch through the sampler
   (a DataLoader cannot take both a sampler and shuffle=True);
 * ``--bf16 1`` trains with bf16 activations (fp32 parameters, statistics and
-  optimizer state); the default 0 is fp32, the reference's arithmetic.
+  optimizer state); the default 0 is fp32, the reference's arithmetic;
+* ``--dynamic_mix 1`` (default 0: the fixed mixtures, as the reference) replaces the
+  training loader by dynamic_mix.DynamicMixLoader: batches drawn and mixed on the GPU from
+  the s1..sC utterances of --train_dir (``--dm_*`` flags); cross validation is unchanged.
 """
 import argparse
 import os
@@ -114,6 +117,36 @@ parser.add_argument('--visdom_id', default='TasNet training',
 # MI355X path
 parser.add_argument('--bf16', default=0, type=int,
                     help='1: bf16 activations (fp32 parameters, statistics and optimizer state)')
+# dynamic mixing on the device (dynamic_mix.py); 0: the corpus's fixed mixtures, as the reference
+parser.add_argument('--dynamic_mix', default=0, type=int,
+                    help='1: draw and mix every training batch on the GPU from the s1..sC utterances of --train_dir')
+parser.add_argument('--dm_seed', default=0, type=int,
+                    help='Seed of the dynamic-mixing draws')
+parser.add_argument('--dm_level_mode', default=0, type=int, choices=[0, 1],
+                    help='0: level on the stored waveform, 1: relative to the segment RMS')
+parser.add_argument('--dm_level_db', default=[-2.5, 2.5], type=float, nargs=2, metavar=('LO', 'HI'),
+                    help='Range of the uniform per-source level draw (dB)')
+parser.add_argument('--dm_peak', default=0.9, type=float,
+                    help='Mixtures peaking above this are scaled down to it (0: off)')
+parser.add_argument('--dm_steps', default=0, type=int,
+                    help='Steps per epoch (0: the number of minibatches the static loader gives this rank)')
+
+
+def dynamic_mix_loader(args, static_loader, rank, world):
+    """The training loader of --dynamic_mix 1 (cross validation keeps the fixed set)."""
+    if not args.use_cuda:
+        raise ValueError("--dynamic_mix 1 mixes on the GPU: it cannot be combined with --use_cuda 0")
+    from dynamic_mix import DeviceCorpus, DynamicMixer, DynamicMixLoader
+    corpus = DeviceCorpus.from_json_dir(args.train_dir, args.sample_rate,
+                                        device=torch.device("cuda", torch.cuda.current_device()))
+    mixer = DynamicMixer(corpus, args.batch_size, args.C, int(args.segment * args.sample_rate), seed=args.dm_seed,
+                         level_mode=args.dm_level_mode, level_db=tuple(args.dm_level_db), peak=args.dm_peak,
+                         rank=rank, world=world)
+    steps = args.dm_steps if args.dm_steps > 0 else len(static_loader)
+    if rank == 0:
+        print("Dynamic mixing: {} utterances ({:.1f} MB on the device), {} steps per epoch".format(
+            corpus.n_utts, corpus.nbytes / 1e6, steps))
+    return DynamicMixLoader(mixer, steps)
 
 
 class Single(torch.nn.Module):
@@ -140,6 +173,8 @@ class FlatDP(Single):
 
 
 def main(args):
+    if args.dynamic_mix and not args.use_cuda:
+        raise ValueError("--dynamic_mix 1 mixes on the GPU: it cannot be combined with --use_cuda 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -157,6 +192,8 @@ def main(args):
                                 num_workers=args.num_workers)
     cv_loader = AudioDataLoader(cv_dataset, batch_size=1,
                                 sampler=MinibatchSampler(cv_dataset, rank, world, drop_last=False), num_workers=0)
+    if args.dynamic_mix:
+        tr_loader = dynamic_mix_loader(args, tr_loader, rank, world)
     data = {'tr_loader': tr_loader, 'cv_loader': cv_loader}
     # model
     model = ConvTasNet(args.N, args.L, args.B, args.H, args.P, args.X, args.R,

@@ -246,6 +246,59 @@ int ctn_bss_eval(const ctn_bss_desc* d, const float* refs /*[M][C][T]*/, const f
                  void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Dynamic mixing: training batches drawn and mixed on the device from a resident corpus
+ * of single-speaker utterances, instead of the host collation of fixed mixtures
+ * (src/data.py:131-159 _collate_fn, :237-271 load_mixtures_and_sources).  Added within ABI v13
+ * without a version bump (nothing existing changed): callers probe for the symbol.
+ * Corpus (caller-owned device memory): `pool`, all utterances back to back — pool_dtype 0:
+ * int16 PCM, a sample s has the value s * 2^-15; 1: fp32 —, `off` [n_utts + 1] sample
+ * offsets, `spk` [n_utts] speaker ids, `elig` [n_elig] the utterances of at least T samples.
+ *
+ * ctn_dmix_draw fills plan[M][C].  Row m is global sample g = first_sample + m; the random
+ * words of slot c, try j are Philox4x32-10 with counter (g_lo, g_hi, c, j) and key
+ * (seed_lo, seed_hi): utt = elig[(r0 * n_elig) >> 32], start = (r1 * (len - T + 1)) >> 32,
+ * level_db = lo + (hi - lo) * (r2 >> 8) * 2^-24 (fp32).  Slots are drawn in order; a
+ * candidate whose speaker equals an accepted earlier slot's is rejected and j advances;
+ * after max_tries candidates the last one is kept; `tries` = candidates drawn.  A row
+ * depends on (seed, g) only.  An elig entry outside [0, n_utts), or naming an utterance
+ * shorter than T or of 2^31 samples or more, gives utt = -1 (which ctn_dmix_mix flags).
+ * first_sample_dev != NULL: g is read from that device word (first_sample is ignored) and a
+ * second kernel then adds `advance` to it, so that a captured launch replays correctly.
+ *
+ * ctn_dmix_mix takes a plan (drawn, or written by the caller).  Gain of (m, c) before the
+ * guard: level_mode 0: 10^(level_db / 20); 1: 10^(level_db / 20) / max(rms, 1e-4), rms over
+ * the segment's T samples (fp64, per-chunk partial sums finished in index order).  peak > 0:
+ * p = max_t |sum_c fl32(g_c x_c)|; if p > peak every gain of the row becomes
+ * fl32(g_c * fl32(peak / p)).  gains[m][c] is the gain applied;
+ * sources[m][c][t] = fl32(gains[m][c] * x) (x exact, one rounding); mixture[m][t] = the fp32
+ * sum of the stored sources added left to right from c = 0; no FMA contraction anywhere.
+ * An entry with utt outside [0, n_utts), start < 0 or start + T > len is never
+ * dereferenced: its row (sources, mixture, gains) is written as zeros and status[m] = 1,
+ * else status[m] = 0.  No atomics; every sum and max has a fixed order.
+ * Limits: M >= 1, 1 <= C <= 16, T >= 1, n_utts >= 1, n_elig >= 1, 1 <= max_tries <= 64,
+ * pool_dtype and level_mode 0 or 1, finite levels and peak (0 workspace bytes / an error
+ * code beyond).
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t M, C, T;          /* rows, slots (speakers) per row, samples per segment */
+  int32_t n_utts, n_elig;
+  int32_t pool_dtype;       /* 0 int16 PCM, 1 fp32 */
+  int32_t level_mode;       /* 0 gain from level_db alone, 1 relative to the segment RMS */
+  int32_t max_tries;
+  float level_lo_db, level_hi_db;
+  float peak;               /* 0: no peak guard */
+  uint64_t seed;
+} ctn_dmix_desc;
+typedef struct { int32_t utt, start; float level_db; int32_t tries; } ctn_dmix_entry;
+size_t ctn_dmix_workspace_bytes(const ctn_dmix_desc* d);
+int ctn_dmix_draw(const ctn_dmix_desc* d, const int64_t* off /*[n_utts+1]*/, const int32_t* spk /*[n_utts]*/,
+                  const int32_t* elig /*[n_elig]*/, int64_t first_sample, int64_t* first_sample_dev,
+                  int64_t advance, ctn_dmix_entry* plan /*[M][C]*/, void* stream);
+int ctn_dmix_mix(const ctn_dmix_desc* d, const void* pool, const int64_t* off /*[n_utts+1]*/,
+                 const ctn_dmix_entry* plan /*[M][C]*/, float* gains /*[M][C]*/, float* sources /*[M][C][T]*/,
+                 float* mixture /*[M][T]*/, int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
  * Parameter update: replaces torch.nn.utils.clip_grad_norm_(params, max_norm)
  * (src/solver.py:184-185) and torch.optim.Adam(params, lr, weight_decay=l2)
  * (src/train.py:129-133, stepped at src/solver.py:186) with one launch each
