@@ -10,6 +10,7 @@ namespace ctn {
 constexpr int DMIX_MAX_C = 16;        // slots per row (the PIT loss's limit)
 constexpr int DMIX_MAX_TRIES = 64;    // candidates per slot
 constexpr int DMIX_CHUNK = 2048;      // samples per workgroup: 256 threads x 8
+constexpr int DMIX_MAX_SPEEDS = 8;    // entries of a speed table (ctn_dmix_draw_sp, ctn_dmix_mix_sp)
 
 struct DmixEntry {                    // == ctn_dmix_entry
   int32_t utt, start;
@@ -37,6 +38,9 @@ struct DmixDrawArgs {
   int64_t* first_dev;
   int64_t advance;            // added to *first_dev by a second kernel
   DmixEntry* plan;            // [M][C]
+  int32_t* speed;             // [M][C] speed index of each slot, or null: the plain draw
+  int32_t nspeed;             // with `speed`: entries of `span`
+  int64_t span[DMIX_MAX_SPEEDS];   // with `speed`: input samples a segment of speed k needs
 };
 
 struct DmixMixArgs {
@@ -53,8 +57,52 @@ struct DmixMixArgs {
   DmixLayout L;
 };
 
+// Speed perturbation (ctn_dmix_draw_sp, ctn_dmix_mix_sp).
+constexpr int DMIX_MAX_RATIO = 64;    // up, down <= 64; up <= 2 down, down <= 2 up
+// Input window of one chunk: (DMIX_CHUNK - 1) * down / up + 2 * Hl / up + 2 <= 4094 + 40 + 2
+// samples, staged in groups of 8.
+constexpr int DMIX_SP_WINDOW = 4160;
+constexpr int DMIX_SP_TAPS = 2 * 10 * DMIX_MAX_RATIO + 1;   // 2 Hl + 1 <= 1281
+
+struct DmixSpeed {
+  int32_t up, down, hl;   // hl = 10 * max(up, down); the filter has 2 hl + 1 taps
+  int32_t foff;           // first tap in the filter table (1/1: no taps)
+  int64_t span;           // floor((T - 1) * down / up) + 1: input samples under the T outputs' centres
+};
+
+struct DmixSpeedTable {
+  int32_t n;
+  DmixSpeed s[DMIX_MAX_SPEEDS];
+};
+
+// Byte offsets into the caller's workspace of ctn_dmix_mix_sp: the plain mix's own workspace
+// first, then the resampled segments and the tables that present them to the mix kernels as an
+// fp32 pool of M*C utterances of T samples.
+struct DmixSpLayout {
+  DmixLayout mix;
+  size_t off_xr;       // float [M*C][T]
+  size_t off_plan;     // DmixEntry [M*C]: {utt = m*C + c or -1, start = 0, level_db, tries}
+  size_t off_off;      // int64 [M*C + 1]: (m*C + c) * T
+  size_t bytes;
+};
+
+struct DmixResampleArgs {
+  int M, C, T, U, pool_dtype;
+  DmixSpeedTable sp;
+  const float* filt;          // the table's filters, back to back
+  const void* pool;
+  const int64_t* off;         // [U+1]
+  const DmixEntry* plan;      // [M][C]
+  const int32_t* speed;       // [M][C]
+  char* ws;
+  DmixSpLayout L;
+};
+
 DmixLayout dmix_layout(int M, int C, int T);
+DmixSpLayout dmix_sp_layout(int M, int C, int T);
 hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s);
 hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s);
+// a.plan, a.off, a.pool, a.U, a.pool_dtype of `mix` are replaced by the resampled pool's.
+hipError_t launch_dmix_mix_sp(const DmixResampleArgs& r, DmixMixArgs mix, hipStream_t s);
 
 }  // namespace ctn

@@ -1,10 +1,13 @@
-// Dynamic mixing on the device (include/ctn.h: ctn_dmix_draw, ctn_dmix_mix).
+// Dynamic mixing on the device (include/ctn.h: ctn_dmix_draw, ctn_dmix_mix, ctn_dmix_draw_sp,
+// ctn_dmix_mix_sp).
 //
 // draw : one thread per batch row; Philox4x32-10 counter (g_lo, g_hi, slot, try), key = seed.
 // mix  : ssq   (level_mode 1) per-chunk sums of squares of every segment, fp64
 //        gain0 one thread per row: validity, status, gains before the guard
 //        peak  (peak > 0) per-chunk max |sum_c fl32(g_c x_c)| of every row
 //        write final gains, sources, mixture
+// mix_sp: resample (every segment through its speed's polyphase FIR into the workspace),
+//        then the mix kernels above on the resampled segments
 // A workgroup of 256 threads covers DMIX_CHUNK = 2048 consecutive samples of one segment
 // (ssq) or one row (peak, write), 8 per thread.  A segment starts at any sample of the pool,
 // so an int16 segment at any 2-byte and the fp32 rows (T is arbitrary) at any 4-byte
@@ -55,7 +58,9 @@ CTN_DEV Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
   return Philox{{c0, c1, c2, c3}};
 }
 
-__global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
+// SP: the slot's speed index k = (r3 * S) >> 32 is drawn first and the segment needs span[k]
+// input samples instead of T (ctn_dmix_draw_sp); one entry of ratio 1/1 gives the plain plan.
+template <bool SP> __global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
   const int m = blockIdx.x * 64 + threadIdx.x;
   if (m >= a.M) return;
   const uint64_t g = (uint64_t)((a.first_dev ? *a.first_dev : a.first) + m);
@@ -63,9 +68,14 @@ __global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
   uint32_t valid = 0;
   for (int c = 0; c < a.C; ++c) {
     DmixEntry e{-1, 0, 0.f, 0};
-    int32_t sp = 0;
+    int32_t sp = 0, k = 0;
     for (int j = 0; j < a.max_tries; ++j) {
       const Philox r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), (uint32_t)c, (uint32_t)j, a.seed_lo, a.seed_hi);
+      int64_t need = a.T;
+      if constexpr (SP) {
+        k = (int32_t)(((uint64_t)r.r[3] * (uint64_t)a.nspeed) >> 32);
+        need = a.span[k];
+      }
       const int32_t utt = a.elig[((uint64_t)r.r[0] * (uint64_t)a.E) >> 32];
       const float u = (float)(r.r[2] >> 8) * 0x1p-24f;
       e.level_db = a.lo_db + (a.hi_db - a.lo_db) * u;
@@ -73,7 +83,7 @@ __global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
       e.utt = -1;
       e.start = 0;
       if (utt < 0 || utt >= a.U) break;                    // a bad table entry: flagged by the mix
-      const int64_t n = a.off[utt + 1] - a.off[utt] - a.T + 1;
+      const int64_t n = a.off[utt + 1] - a.off[utt] - need + 1;
       if (n < 1 || n > 0x7fffffffLL) break;
       e.utt = utt;
       e.start = (int32_t)(((uint64_t)r.r[1] * (uint64_t)n) >> 32);
@@ -85,13 +95,15 @@ __global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
     taken[c] = sp;
     if (e.utt >= 0) valid |= 1u << c;
     a.plan[(size_t)m * a.C + c] = e;
+    if constexpr (SP) a.speed[(size_t)m * a.C + c] = k;
   }
 }
 
 __global__ void dmix_advance_kernel(int64_t* first, int64_t advance) { *first += advance; }
 
 hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s) {
-  dmix_draw_kernel<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+  if (a.speed) dmix_draw_kernel<true><<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+  else dmix_draw_kernel<false><<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
   if (a.first_dev) dmix_advance_kernel<<<dim3(1), dim3(1), 0, s>>>(a.first_dev, a.advance);
   return hipGetLastError();
 }
@@ -298,6 +310,137 @@ hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s) {
   if (i16) dmix_write_kernel<0><<<rows, blk, 0, s>>>(a);
   else dmix_write_kernel<1><<<rows, blk, 0, s>>>(a);
   return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// speed perturbation: polyphase resampling of every segment, then the mix above
+// ---------------------------------------------------------------------------
+static_assert(DMIX_SP_WINDOW % 8 == 0 && DMIX_SP_WINDOW >= 2 * (DMIX_CHUNK - 1) + 40 + 2 + 7, "chunk window");
+
+DmixSpLayout dmix_sp_layout(int M, int C, int T) {
+  DmixSpLayout L{};
+  L.mix = dmix_layout(M, C, T);
+  const size_t mc = (size_t)M * C;
+  size_t o = (L.mix.bytes + 15) / 16 * 16;
+  L.off_xr = o;   o += (mc * (size_t)T * sizeof(float) + 15) / 16 * 16;
+  L.off_plan = o; o += mc * sizeof(DmixEntry);
+  L.off_off = o;  o += (mc + 1) * sizeof(int64_t);
+  L.bytes = o;
+  return L;
+}
+
+CTN_DEV int64_t floor_div(int64_t a, int64_t b) {   // b > 0
+  const int64_t q = a / b;
+  return q * b > a ? q - 1 : q;
+}
+
+// First pool sample of the entry's utterance and the utterance's length, or false for an
+// entry that must not be read: the T output centres span sp.span input samples from `start`.
+CTN_DEV bool sp_entry(const DmixResampleArgs& a, const DmixEntry& e, int32_t k, int64_t* o, int64_t* len) {
+  if (k < 0 || k >= a.sp.n || e.utt < 0 || e.utt >= a.U || e.start < 0) return false;
+  *o = a.off[e.utt];
+  *len = a.off[e.utt + 1] - *o;
+  return (int64_t)e.start + a.sp.s[k].span <= *len;
+}
+
+// xr[n] = sum_i h[n down - i up + hl] x[i], i upward, acc = fl32(acc + fl32(h x)) from 0
+// (include/ctn.h).  grid: (m*C + c) * nchunk + chunk; thread t computes the chunk's outputs
+// t, t + 256, ...: neighbouring lanes are neighbouring outputs, whose filter phases
+// p = (n down + hl) mod up are distinct (or equal: a broadcast) and whose newest inputs
+// q = (n down + hl) / up are at most 2 apart.  With the tap index j = (h index - p) / up the
+// same in every lane, the h words of a wave-instruction are p + j up: h in its natural order
+// is already the [tap][phase] layout, conflict-free for up <= 32 and 2-way above.
+// Input samples outside the utterance are staged as +0 and never read from the pool; adding
+// fl32(h * 0) = +-0 to a sum that started at +0 leaves its bits, so this equals skipping them.
+template <int DT> __global__ __launch_bounds__(256) void dmix_resample_kernel(DmixResampleArgs a) {
+  __shared__ float xw[DMIX_SP_WINDOW];
+  __shared__ float hs[DMIX_SP_TAPS + 3];
+  const int nchunk = a.L.mix.nchunk;
+  const int mc = blockIdx.x / nchunk, chunk = blockIdx.x % nchunk;
+  const int tid = threadIdx.x;
+  const DmixEntry e = a.plan[mc];
+  const int32_t k = a.speed[mc];
+  int64_t o = 0, len = 0;
+  const bool ok = sp_entry(a, e, k, &o, &len);
+  if (chunk == 0 && tid == 0) {   // the tables that present xr to the mix kernels
+    reinterpret_cast<DmixEntry*>(a.ws + a.L.off_plan)[mc] = DmixEntry{ok ? mc : -1, 0, e.level_db, e.tries};
+    int64_t* off2 = reinterpret_cast<int64_t*>(a.ws + a.L.off_off);
+    off2[mc] = (int64_t)mc * a.T;
+    if (mc == a.M * a.C - 1) off2[mc + 1] = (int64_t)(mc + 1) * a.T;
+  }
+  if (!ok) return;                // utt = -1 above: the mix kernels never read this row of xr
+  float* xr = reinterpret_cast<float*>(a.ws + a.L.off_xr) + (size_t)mc * a.T;
+  const int n0 = chunk * DMIX_CHUNK;
+  const int cnt = min(DMIX_CHUNK, a.T - n0);       // outputs of this chunk, >= 1
+  const DmixSpeed sp = a.sp.s[k];
+  if (sp.up == 1 && sp.down == 1) {                // exact copy
+    float x[8];
+    load8<DT>(a.pool, o + e.start, n0 + tid * 8, a.T, x);
+    store8(xr, n0 + tid * 8, a.T, x);
+    return;
+  }
+  const int up = sp.up, down = sp.down, hl = sp.hl;
+  // segment-relative input indices [ilo, ihi] under the chunk's outputs
+  const int64_t c0 = (int64_t)n0 * down;
+  const int64_t ilo = -floor_div(hl - c0, up);                            // ceil((c0 - hl) / up)
+  const int64_t ihi = floor_div(c0 + (int64_t)(cnt - 1) * down + hl, up);
+  const int W = (int)(ihi - ilo + 1);                                     // <= DMIX_SP_WINDOW - 7
+  for (int t = tid; t <= 2 * hl; t += 256) hs[t] = a.filt[sp.foff + t];
+  const int64_t a0 = (int64_t)e.start + ilo;                              // utterance index of xw[0]
+  for (int g = tid * 8; g < W; g += 256 * 8) {
+    float x[8];
+    const int64_t u = a0 + g;
+    if (u >= 0 && u + 8 <= len) {
+      load8<DT>(a.pool, o + u, 0, 8, x);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        x[i] = 0.f;
+        if (u + i >= 0 && u + i < len) {
+          if constexpr (DT == 0) x[i] = (float)reinterpret_cast<const int16_t*>(a.pool)[o + u + i] * 0x1p-15f;
+          else x[i] = reinterpret_cast<const float*>(a.pool)[o + u + i];
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) xw[g + i] = x[i];
+  }
+  __syncthreads();
+  // output n0 + r: t = c0 + hl + r down = q up + p
+  const int64_t t0 = c0 + hl;
+  const int64_t q0 = t0 / up;
+  const int p0 = (int)(t0 - q0 * up);
+  const int jfull = 2 * hl / up;
+  const unsigned tr = (unsigned)(p0 + tid * down);
+  int p = (int)(tr % (unsigned)up);
+  int qi = (int)(q0 - ilo) + (int)(tr / (unsigned)up);                    // q - ilo: index into xw
+  const int dq = 256 * down / up, dp = 256 * down % up;
+  for (int r = tid; r < cnt; r += 256) {
+    float acc = 0.f;
+    if (p + jfull * up <= 2 * hl) acc = acc + hs[p + jfull * up] * xw[qi - jfull];   // only this tap can be absent
+    for (int j = jfull - 1; j >= 0; --j) acc = acc + hs[p + j * up] * xw[qi - j];
+    xr[n0 + r] = acc;
+    p += dp;
+    qi += dq;
+    if (p >= up) {
+      p -= up;
+      qi += 1;
+    }
+  }
+}
+
+hipError_t launch_dmix_mix_sp(const DmixResampleArgs& r, DmixMixArgs mix, hipStream_t s) {
+  const unsigned segs = (unsigned)((long)r.M * r.C * r.L.mix.nchunk);
+  if (r.pool_dtype == 0) dmix_resample_kernel<0><<<dim3(segs), dim3(256), 0, s>>>(r);
+  else dmix_resample_kernel<1><<<dim3(segs), dim3(256), 0, s>>>(r);
+  mix.U = r.M * r.C;
+  mix.pool_dtype = 1;
+  mix.pool = r.ws + r.L.off_xr;
+  mix.off = reinterpret_cast<const int64_t*>(r.ws + r.L.off_off);
+  mix.plan = reinterpret_cast<const DmixEntry*>(r.ws + r.L.off_plan);
+  mix.ws = r.ws;
+  mix.L = r.L.mix;
+  return launch_dmix_mix(mix, s);
 }
 
 }  // namespace ctn

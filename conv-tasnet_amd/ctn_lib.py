@@ -84,6 +84,15 @@ class DmixEntry(ctypes.Structure):
     _fields_ = [("utt", c_int32), ("start", c_int32), ("level_db", ctypes.c_float), ("tries", c_int32)]
 
 
+class DmixRatio(ctypes.Structure):
+    _fields_ = [("up", c_int32), ("down", c_int32)]
+
+
+class DmixSpeeds(ctypes.Structure):
+    """ctn_dmix_speeds: the speed table of ctn_dmix_draw_sp / ctn_dmix_mix_sp."""
+    _fields_ = [("n", c_int32), ("r", DmixRatio * 8)]
+
+
 MASK_IDENTITY = 2
 
 
@@ -158,6 +167,11 @@ _SIGS = {
     "ctn_dmix_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_dmix_draw": (ctypes.c_int, [c_void_p] * 4 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "ctn_dmix_mix": (ctypes.c_int, [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_dmix_sp_filter_floats": (c_size_t, [c_void_p]),
+    "ctn_dmix_sp_workspace_bytes": (c_size_t, [c_void_p, c_void_p]),
+    "ctn_dmix_draw_sp": (ctypes.c_int, [c_void_p] * 5 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
+                                                         c_void_p]),
+    "ctn_dmix_mix_sp": (ctypes.c_int, [c_void_p] * 11 + [c_void_p, c_size_t, c_void_p]),
     "ctn_pack_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "ctn_opt_plan": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int]),
     "ctn_grad_clip_norm": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_float, c_void_p, c_void_p,

@@ -14,6 +14,11 @@ how a global batch is split over ranks.
 a batch can be reproduced on the host without a GPU (and the tests use them as the
 reference).  ``mix_host`` computes its gains in fp64; given the gains a device call
 reported it reproduces that call's sources and mixture bit for bit.
+
+Speed perturbation (``DynamicMixer(..., speeds=(95, 100, 105))``): every
+source is resampled on the device by a polyphase FIR before it is mixed
+(ctn_dmix_draw_sp, ctn_dmix_mix_sp).  ``speed_ratio``, ``speed_filter``, ``segment_span``
+and ``resample_host`` restate it, and ``plan_host`` / ``mix_host`` take ``speeds``.
 """
 from __future__ import annotations
 
@@ -48,23 +53,100 @@ def eligible(off, T):
     return np.nonzero(np.diff(off) >= T)[0].astype(np.int32)
 
 
-def plan_host(off, spk, elig, M, C, T, seed=0, first_sample=0, level_db=(-2.5, 2.5), max_tries=16):
-    """The plan ctn_dmix_draw writes: a [M, C] array of PLAN_DTYPE."""
+MAX_SPEEDS, MAX_RATIO = 8, 64
+
+
+def speed_ratio(pct):
+    """Speed in percent -> the reduced resampling ratio (up, down), output rate over input
+    rate: up/down = 100/pct, so 95 -> (20, 19) and 105 -> (20, 21).  ValueError outside the
+    library's limits (1 <= up, down <= 64, up <= 2 down, down <= 2 up)."""
+    if isinstance(pct, bool) or int(pct) != pct or int(pct) < 1:
+        raise ValueError(f"speed {pct!r}: a positive integer percent")
+    g = np.gcd(100, int(pct))
+    up, down = 100 // int(g), int(pct) // int(g)
+    if up > MAX_RATIO or down > MAX_RATIO or up > 2 * down or down > 2 * up:
+        raise ValueError(f"speed {pct} % is the ratio {up}/{down}: outside the limits (up, down <= {MAX_RATIO}, "
+                         f"between 1/2 and 2)")
+    return up, down
+
+
+def _speed_filter64(up, down):
+    hl = 10 * max(up, down)
+    n = np.arange(-hl, hl + 1, dtype=np.float64)
+    fc = 1.0 / max(up, down)
+    h = fc * np.sinc(fc * n) * np.kaiser(2 * hl + 1, 5.0)
+    return h / h.sum() * up, hl
+
+
+def speed_filter(up, down):
+    """(h float32 [2 Hl + 1], Hl): the filter of scipy.signal.resample_poly(x, up, down) —
+    Hl = 10 max(up, down), a sinc of cut-off 1/max(up, down) under a Kaiser window (beta 5),
+    unit sum, times up; computed in fp64 and rounded once."""
+    h, hl = _speed_filter64(up, down)
+    return h.astype(np.float32), hl
+
+
+def segment_span(T, up, down):
+    """Input samples under the centres of T outputs: floor((T - 1) down / up) + 1."""
+    return (int(T) - 1) * int(down) // int(up) + 1
+
+
+def resample_host(wave_f32, start, T, up, down):
+    """The resampled segment of ctn_dmix_mix_sp: xr[n] = sum_i h[n down - i up + Hl] x[i],
+    x[i] = wave[start + i], for n = 0 ... T - 1; i upward, acc = fl32(acc + fl32(h x)) from 0;
+    terms whose x lies outside the wave are skipped.  1/1: the samples themselves."""
+    x = np.asarray(wave_f32, np.float32)
+    n = np.arange(T, dtype=np.int64)
+    if len(x) == 0:
+        return np.zeros(T, np.float32)
+    if (up, down) == (1, 1):
+        a = int(start) + n
+        ok = (a >= 0) & (a < len(x))
+        out = np.zeros(T, np.float32)
+        out[ok] = x[a[ok]]
+        return out
+    h, hl = speed_filter(up, down)
+    t = n * down + hl
+    q, p = t // up, t % up
+    acc = np.zeros(T, np.float32)
+    for j in range(2 * hl // up, -1, -1):                # i = q - j runs upward
+        hi, a = p + j * up, int(start) + q - j
+        ok = (hi <= 2 * hl) & (a >= 0) & (a < len(x))
+        term = h[np.where(ok, hi, 0)] * x[np.where(ok, a, 0)]        # fp32 product, one rounding
+        acc = np.where(ok, acc + term, acc)
+    return acc
+
+
+def _speed_table(speeds):
+    """Percents -> [(up, down)] (1 to 8 entries)."""
+    ratios = [speed_ratio(p) for p in speeds]
+    if not 1 <= len(ratios) <= MAX_SPEEDS:
+        raise ValueError(f"{len(ratios)} speeds: 1 to {MAX_SPEEDS}")
+    return ratios
+
+
+def plan_host(off, spk, elig, M, C, T, seed=0, first_sample=0, level_db=(-2.5, 2.5), max_tries=16, speeds=None):
+    """The plan ctn_dmix_draw writes: a [M, C] array of PLAN_DTYPE.  With `speeds` (percents):
+    (plan, speed_idx [M, C] int32) as ctn_dmix_draw_sp writes them; `elig` should then hold
+    the utterances of at least max_k segment_span(T, up_k, down_k) samples."""
     off, spk, elig = np.asarray(off, np.int64), np.asarray(spk, np.int32), np.asarray(elig, np.int32)
     U, E = len(spk), len(elig)
     lo, hi = np.float32(level_db[0]), np.float32(level_db[1])
     key = (int(seed) & _U32, (int(seed) >> 32) & _U32)
     plan = np.zeros((M, C), dtype=PLAN_DTYPE)
+    spans = [T] if speeds is None else [segment_span(T, up, down) for up, down in _speed_table(speeds)]
+    speed_idx = np.zeros((M, C), np.int32)
     for m in range(M):
         g = (int(first_sample) + m) & 0xFFFFFFFFFFFFFFFF
         taken = []                                       # speakers of the accepted valid slots
         for c in range(C):
             for j in range(max_tries):
                 r = philox4x32_10((g & _U32, g >> 32, c, j), key)
+                k = (r[3] * len(spans)) >> 32
                 utt = int(elig[(r[0] * E) >> 32])
                 level = lo + (hi - lo) * (np.float32(r[2] >> 8) * np.float32(2.0 ** -24))
                 e = (-1, 0, level, j + 1)
-                n = int(off[utt + 1] - off[utt]) - T + 1 if 0 <= utt < U else 0
+                n = int(off[utt + 1] - off[utt]) - spans[k] + 1 if 0 <= utt < U else 0
                 if n < 1 or n > 0x7FFFFFFF:
                     sp = None
                     break
@@ -73,25 +155,36 @@ def plan_host(off, spk, elig, M, C, T, seed=0, first_sample=0, level_db=(-2.5, 2
                 if sp not in taken:
                     break
             plan[m, c] = e
+            speed_idx[m, c] = k
             if sp is not None and e[0] >= 0:
                 taken.append(sp)
-    return plan
+    return plan if speeds is None else (plan, speed_idx)
 
 
-def _segment(pool, off, e, T):
-    """fp32 samples of a plan entry, or None for an entry that must not be read."""
+def _segment(pool, off, e, T, ratios=None, k=0):
+    """fp32 samples of a plan entry (resampled at ratios[k] when given), or None for an
+    entry that must not be read."""
     U = len(off) - 1
     utt, start = int(e["utt"]), int(e["start"])
-    if not 0 <= utt < U or start < 0 or start + T > int(off[utt + 1] - off[utt]):
+    if ratios is not None and not 0 <= k < len(ratios):
         return None
+    up, down = (1, 1) if ratios is None else ratios[k]
+    if not 0 <= utt < U or start < 0 or start + segment_span(T, up, down) > int(off[utt + 1] - off[utt]):
+        return None
+    if (up, down) != (1, 1):
+        x = pool[int(off[utt]):int(off[utt + 1])]
+        x = x.astype(np.float32) * np.float32(2.0 ** -15) if x.dtype == np.int16 else x.astype(np.float32, copy=False)
+        return resample_host(x, start, T, up, down)
     x = pool[int(off[utt]) + start:int(off[utt]) + start + T]
     if x.dtype == np.int16:
         return x.astype(np.float32) * np.float32(2.0 ** -15)
     return x.astype(np.float32, copy=False)
 
 
-def mix_host(pool, off, plan, T, level_mode=0, peak=0.9, gains=None):
+def mix_host(pool, off, plan, T, level_mode=0, peak=0.9, gains=None, speeds=None, speed_idx=None):
     """ctn_dmix_mix on the host.  pool: int16 or float32 [n]; plan: [M, C] PLAN_DTYPE.
+    With `speeds` (percents) and `speed_idx` [M, C]: ctn_dmix_mix_sp, every segment resampled
+    (resample_host) before the level, RMS and peak stages.
 
     -> dict(gains [M, C] float64: the gains in fp64 arithmetic; p [M] float64: the
     unguarded mixture's peak; sources [M, C, T], mixture [M, T] float32; status [M] int32).
@@ -102,8 +195,12 @@ def mix_host(pool, off, plan, T, level_mode=0, peak=0.9, gains=None):
     g64, p64 = np.zeros((M, C)), np.zeros(M)
     sources, mixture = np.zeros((M, C, T), np.float32), np.zeros((M, T), np.float32)
     status = np.zeros(M, np.int32)
+    ratios = None if speeds is None else _speed_table(speeds)
+    if ratios is not None and (speed_idx is None or np.shape(speed_idx) != (M, C)):
+        raise ValueError(f"speeds need speed_idx of shape {(M, C)}")
     for m in range(M):
-        xs = [_segment(pool, off, plan[m, c], T) for c in range(C)]
+        xs = [_segment(pool, off, plan[m, c], T, ratios, 0 if ratios is None else int(speed_idx[m, c]))
+              for c in range(C)]
         if any(x is None for x in xs):
             status[m] = 1
             continue
@@ -230,10 +327,14 @@ class DynamicMixer:
 
     level_mode 0: gain 10^(level_db / 20) on the stored waveform; 1: relative to the
     segment's RMS (floored at 1e-4).  level_db: (lo, hi) of the uniform level draw.
-    peak > 0: a row whose mixture would exceed it is scaled down to it."""
+    peak > 0: a row whose mixture would exceed it is scaled down to it.
+    speeds: integer percents, e.g. (95, 100, 105): every source is played at one of them,
+    drawn per slot, through the library's polyphase resampler (ctn_dmix_draw_sp,
+    ctn_dmix_mix_sp; `.speed` holds the drawn indices).  None or all 100: no resampling, the
+    plain entry points."""
 
     def __init__(self, corpus, M, C, T, seed=0, level_mode=0, level_db=(-2.5, 2.5), peak=0.9, max_tries=16,
-                 rank=0, world=1):
+                 rank=0, world=1, speeds=None):
         import torch
 
         import ctn_lib as L
@@ -242,13 +343,29 @@ class DynamicMixer:
         L.require_device(corpus.pool, "DynamicMixer")
         self.corpus, self.M, self.C, self.T = corpus, int(M), int(C), int(T)
         self.rank, self.world = int(rank), int(world)
-        self.elig, self.elig_host = corpus.eligible(self.T, self.C)
+        ratios = None if speeds is None else _speed_table(speeds)
+        if ratios is not None and all(r == (1, 1) for r in ratios):
+            ratios = None
+        self.speeds = None if ratios is None else tuple(int(p) for p in speeds)
+        self.ratios = ratios
+        need = self.T if ratios is None else max(segment_span(self.T, up, down) for up, down in ratios)
+        self.elig, self.elig_host = corpus.eligible(need, self.C)
         self.desc = L.DmixDesc(M=self.M, C=self.C, T=self.T, n_utts=corpus.n_utts, n_elig=len(self.elig_host),
                                pool_dtype=corpus.pool_dtype, level_mode=int(level_mode), max_tries=int(max_tries),
                                level_lo_db=float(level_db[0]), level_hi_db=float(level_db[1]), peak=float(peak),
                                seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._lib = L.load()
-        nbytes = self._lib.ctn_dmix_workspace_bytes(ctypes.byref(self.desc))
+        self.speed = self._filt = self._sp = None
+        if ratios is None:
+            nbytes = self._lib.ctn_dmix_workspace_bytes(ctypes.byref(self.desc))
+        else:
+            self._sp = L.DmixSpeeds(n=len(ratios))
+            for k, (up, down) in enumerate(ratios):
+                self._sp.r[k].up, self._sp.r[k].down = up, down
+            nbytes = self._lib.ctn_dmix_sp_workspace_bytes(ctypes.byref(self.desc), ctypes.byref(self._sp))
+            if nbytes == 0:                              # raises with the library's reason
+                L.check(self._lib.ctn_dmix_draw_sp(ctypes.byref(self.desc), ctypes.byref(self._sp), None, None, None,
+                                                   0, None, 0, None, None, None), "DynamicMixer")
         if nbytes == 0:
             L.check(self._lib.ctn_dmix_draw(ctypes.byref(self.desc), None, None, None, 0, None, 0, None, None),
                     "DynamicMixer")                     # raises with the library's reason
@@ -258,6 +375,13 @@ class DynamicMixer:
         self.gains = torch.zeros(self.M, self.C, dtype=torch.float32, device=dev)
         self.status = torch.zeros(self.M, dtype=torch.int32, device=dev)
         self.lengths = torch.full((self.M,), self.T, dtype=torch.int64, device=dev)
+        if ratios is not None:
+            taps = np.concatenate([speed_filter(up, down)[0] for up, down in ratios if (up, down) != (1, 1)])
+            if len(taps) != self._lib.ctn_dmix_sp_filter_floats(ctypes.byref(self._sp)):
+                raise L.CtnLibraryError(f"filter table of {len(taps)} taps, the library expects "
+                                        f"{self._lib.ctn_dmix_sp_filter_floats(ctypes.byref(self._sp))}")
+            self._filt = torch.from_numpy(taps).to(dev)
+            self.speed = torch.zeros(self.M, self.C, dtype=torch.int32, device=dev)
 
     def first_sample(self, step):
         return (int(step) * self.world + self.rank) * self.M
@@ -279,25 +403,43 @@ class DynamicMixer:
         c = self.corpus
         if counter is not None:
             self._checked(counter, "counter", torch.int64, (1,))
+        if self.ratios is not None:
+            L.check(self._lib.ctn_dmix_draw_sp(ctypes.byref(self.desc), ctypes.byref(self._sp), L.ptr(c.off),
+                                               L.ptr(c.spk), L.ptr(self.elig), int(first_sample), L.ptr(counter),
+                                               int(advance), L.ptr(self.plan), L.ptr(self.speed),
+                                               L.stream_handle(c.device)), "ctn_dmix_draw_sp")
+            return self.plan
         L.check(self._lib.ctn_dmix_draw(ctypes.byref(self.desc), L.ptr(c.off), L.ptr(c.spk), L.ptr(self.elig),
                                         int(first_sample), L.ptr(counter), int(advance), L.ptr(self.plan),
                                         L.stream_handle(c.device)), "ctn_dmix_draw")
         return self.plan
 
-    def mix(self, plan=None, sources=None, mixture=None):
-        """Mix `plan` (default: the last drawn) -> (mixture [M, T], sources [M, C, T])."""
+    def mix(self, plan=None, sources=None, mixture=None, speed=None):
+        """Mix `plan` (default: the last drawn) -> (mixture [M, T], sources [M, C, T]).
+        speed: with speeds, the int32 [M, C] speed indices of `plan` (default: the last drawn)."""
         import torch
 
         import ctn_lib as L
         c = self.corpus
         if plan is not None:
             self.plan = self._checked(plan, "plan", torch.int32, (self.M, self.C, 4))
+        if speed is not None:
+            if self.ratios is None:
+                raise ValueError("speed: this mixer was built without speeds")
+            self.speed = self._checked(speed, "speed", torch.int32, (self.M, self.C))
         if sources is None:
             sources = torch.empty(self.M, self.C, self.T, dtype=torch.float32, device=c.device)
         if mixture is None:
             mixture = torch.empty(self.M, self.T, dtype=torch.float32, device=c.device)
         self._checked(sources, "sources", torch.float32, (self.M, self.C, self.T))
         self._checked(mixture, "mixture", torch.float32, (self.M, self.T))
+        if self.ratios is not None:
+            L.check(self._lib.ctn_dmix_mix_sp(ctypes.byref(self.desc), ctypes.byref(self._sp), L.ptr(self._filt),
+                                              L.ptr(c.pool), L.ptr(c.off), L.ptr(self.plan), L.ptr(self.speed),
+                                              L.ptr(self.gains), L.ptr(sources), L.ptr(mixture), L.ptr(self.status),
+                                              L.ptr(self._ws), self._ws.numel(), L.stream_handle(c.device)),
+                    "ctn_dmix_mix_sp")
+            return mixture, sources
         L.check(self._lib.ctn_dmix_mix(ctypes.byref(self.desc), L.ptr(c.pool), L.ptr(c.off), L.ptr(self.plan),
                                        L.ptr(self.gains), L.ptr(sources), L.ptr(mixture), L.ptr(self.status),
                                        L.ptr(self._ws), self._ws.numel(), L.stream_handle(c.device)), "ctn_dmix_mix")

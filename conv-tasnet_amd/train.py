@@ -20,6 +20,8 @@ Differences, each deliberate:
 * ``--dynamic_mix 1`` (default 0: the fixed mixtures, as the reference) replaces the
   training loader by dynamic_mix.DynamicMixLoader: batches drawn and mixed on the GPU from
   the s1..sC utterances of --train_dir (``--dm_*`` flags); cross validation is unchanged.
+  ``--dm_speeds 95 100 105`` adds speed perturbation: each source is resampled on the GPU to
+  one of these speeds before it is mixed.
 """
 import argparse
 import os
@@ -130,6 +132,20 @@ parser.add_argument('--dm_peak', default=0.9, type=float,
                     help='Mixtures peaking above this are scaled down to it (0: off)')
 parser.add_argument('--dm_steps', default=0, type=int,
                     help='Steps per epoch (0: the number of minibatches the static loader gives this rank)')
+parser.add_argument('--dm_speeds', default=[100], type=int, nargs='+', metavar='PCT',
+                    help='Speed perturbation: every source is played at one of these percents, drawn per source '
+                         '(e.g. 95 100 105; at most 8; the default 100 is off)')
+
+
+def check_dm_speeds(args):
+    """--dm_speeds needs --dynamic_mix 1 and percents the resampler supports."""
+    from dynamic_mix import _speed_table
+    if any(p != 100 for p in args.dm_speeds) and not args.dynamic_mix:
+        raise ValueError("--dm_speeds perturbs the dynamically mixed sources: it needs --dynamic_mix 1")
+    try:
+        _speed_table(args.dm_speeds)
+    except ValueError as e:
+        raise ValueError(f"--dm_speeds: {e}") from None
 
 
 def dynamic_mix_loader(args, static_loader, rank, world):
@@ -141,7 +157,7 @@ def dynamic_mix_loader(args, static_loader, rank, world):
                                         device=torch.device("cuda", torch.cuda.current_device()))
     mixer = DynamicMixer(corpus, args.batch_size, args.C, int(args.segment * args.sample_rate), seed=args.dm_seed,
                          level_mode=args.dm_level_mode, level_db=tuple(args.dm_level_db), peak=args.dm_peak,
-                         rank=rank, world=world)
+                         rank=rank, world=world, speeds=args.dm_speeds)
     steps = args.dm_steps if args.dm_steps > 0 else len(static_loader)
     if rank == 0:
         print("Dynamic mixing: {} utterances ({:.1f} MB on the device), {} steps per epoch".format(
@@ -173,6 +189,7 @@ class FlatDP(Single):
 
 
 def main(args):
+    check_dm_speeds(args)
     if args.dynamic_mix and not args.use_cuda:
         raise ValueError("--dynamic_mix 1 mixes on the GPU: it cannot be combined with --use_cuda 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -299,6 +299,62 @@ int ctn_dmix_mix(const ctn_dmix_desc* d, const void* pool, const int64_t* off /*
                  float* mixture /*[M][T]*/, int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Dynamic mixing with speed perturbation: every source is resampled by a polyphase FIR
+ * before it is mixed, so that it plays at e.g. 95, 100 or 105 % speed (pitch and tempo
+ * change).  Added like dynamic mixing itself, without an ABI bump: callers probe for the
+ * symbol.  ctn_dmix_draw and ctn_dmix_mix are unchanged.
+ *
+ * Speed table: n entries, 1 <= n <= 8.  Entry k is a reduced ratio up/down, output rate
+ * over input rate; the speed in percent is 100 * down / up (95 % = 20/19, 105 % = 20/21).
+ * Limits: 1 <= up, down <= 64, gcd(up, down) = 1, up <= 2 down, down <= 2 up.  1/1 means
+ * "no resampling".
+ *
+ * Filter of an entry (the design of scipy.signal.resample_poly): Hl = 10 * max(up, down),
+ * 2 Hl + 1 taps, h[n] = fc sinc(fc n) kaiser(2 Hl + 1, beta = 5.0)[n + Hl] for n = -Hl ... Hl
+ * with fc = 1 / max(up, down), normalised to unit sum and multiplied by `up`; computed in
+ * fp64 by the caller and rounded once to fp32.  `filt` (device memory) holds the filters
+ * of the entries back to back, h[-Hl] first, none for a 1/1 entry:
+ * ctn_dmix_sp_filter_floats(speeds) floats.  The kernel evaluates no transcendental.
+ *
+ * Resampled segment of a slot (utt, start, speed k): with x[i] = utt[start + i] as the
+ * exact fp32 value (s * 2^-15 for PCM16) and x[i] = 0 for start + i outside [0, len),
+ *   xr[n] = sum_i h[n down - i up + Hl] x[i],  n = 0 ... T - 1,
+ * i running upward from ceil((n down - Hl) / up) to floor((n down + Hl) / up), each step
+ * acc = fl32(acc + fl32(h x)) from acc = 0, no FMA contraction, int64 index arithmetic.
+ * Terms whose x lies outside the utterance are skipped and never read (the neighbouring
+ * utterance of the pool does not leak in).  For 1/1, xr[n] = x[n] exactly.
+ * span_k = floor((T - 1) down_k / up_k) + 1 input samples lie under the T output centres.
+ * A slot is valid when 0 <= k < n, 0 <= utt < n_utts, 0 <= start and
+ * start + span_k <= len; the filter's tails may overhang the utterance (those taps
+ * contribute zero).  An invalid slot is never dereferenced: its row is zeros and
+ * status[m] = 1, as in ctn_dmix_mix.
+ *
+ * ctn_dmix_draw_sp: the Philox call of ctn_dmix_draw; of each candidate first
+ * k = (r3 * n) >> 32, then utt = elig[(r0 * n_elig) >> 32], then
+ * start = (r1 * (len - span_k + 1)) >> 32 (utt = -1 when len < span_k); level_db, the
+ * speaker rejection, `tries` and the device-counter form are unchanged.  speed[m][c] = k of
+ * the kept candidate.  `elig` should hold the utterances of at least max_k span_k samples.
+ * With the table {1/1} the plan is that of ctn_dmix_draw.
+ *
+ * ctn_dmix_mix_sp: resamples every slot into the workspace (xr [M][C][T]) and runs the
+ * level, RMS, peak-guard and write stages of ctn_dmix_mix on xr, whose contract composes:
+ * sources[m][c][t] = fl32(gains[m][c] * xr), the mixture summed left to right.  With every
+ * slot at 1/1 the outputs are those of ctn_dmix_mix.  Beyond the limits: 0 floats / 0
+ * workspace bytes / an error code.
+ * ------------------------------------------------------------------------- */
+typedef struct { int32_t n; struct { int32_t up, down; } r[8]; } ctn_dmix_speeds;
+size_t ctn_dmix_sp_filter_floats(const ctn_dmix_speeds* speeds);   /* sum of 2 Hl_k + 1; 1/1 entries 0 */
+size_t ctn_dmix_sp_workspace_bytes(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds);
+int ctn_dmix_draw_sp(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds, const int64_t* off /*[n_utts+1]*/,
+                     const int32_t* spk /*[n_utts]*/, const int32_t* elig /*[n_elig]*/, int64_t first_sample,
+                     int64_t* first_sample_dev, int64_t advance, ctn_dmix_entry* plan /*[M][C]*/,
+                     int32_t* speed /*[M][C]*/, void* stream);
+int ctn_dmix_mix_sp(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds, const float* filt, const void* pool,
+                    const int64_t* off /*[n_utts+1]*/, const ctn_dmix_entry* plan /*[M][C]*/,
+                    const int32_t* speed /*[M][C]*/, float* gains /*[M][C]*/, float* sources /*[M][C][T]*/,
+                    float* mixture /*[M][T]*/, int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
  * Parameter update: replaces torch.nn.utils.clip_grad_norm_(params, max_norm)
  * (src/solver.py:184-185) and torch.optim.Adam(params, lr, weight_decay=l2)
  * (src/train.py:129-133, stepped at src/solver.py:186) with one launch each

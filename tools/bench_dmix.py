@@ -7,6 +7,11 @@ utterances, C speakers, T samples:
 
   dmix_ms          dynamic_mix.DynamicMixer.batch on the device: --steps batches queued back to
                    back and synchronized at the end, median of three such windows
+  dmix_speed_ms    the same with speed perturbation (--speeds, default 95 100 105: every source
+                   resampled on the device) beside dmix_long_ms, the unperturbed
+                   batch on the same corpus: a segment at 105 % needs 1.05 T input samples, which
+                   the files of exactly T samples do not hold, so both run on a resident PCM16
+                   corpus of --utts / 2 utterances of 2 T samples per speaker (the same bytes)
   host_loader_ms   the training pipeline as train.py builds it: data.AudioDataLoader over the
                    same files, num_workers 0, 4 and 16 — wall time of a pass of --batches
                    minibatches divided by their number (`steady`: from the arrival of the
@@ -70,9 +75,16 @@ def time_host_loader(json_dir, M, T, workers, batches):
     return {"ms_per_batch": 1e3 * (end - t0) / batches, "steady_ms_per_batch": 1e3 * (end - first) / (batches - 1)}
 
 
-def time_dmix(json_dir, M, C, T, steps):
-    corpus = dynamic_mix.DeviceCorpus.from_json_dir(json_dir, SR, speaker_of=lambda path, slot: (slot, path))
-    mixer = dynamic_mix.DynamicMixer(corpus, M, C, T)
+def long_corpus(utts, C, T):
+    """PCM16 utterances of 2 T samples, utts / 2 per speaker slot, every one its own speaker."""
+    _, src = synthetic.speech_like(max(utts // 2, C), C, 2 * T, 1)
+    pcm = (src * (0.9 * 32767.0 / float(src.abs().max()))).round().to(torch.int16).numpy()
+    waves = [pcm[i, c] for i in range(pcm.shape[0]) for c in range(C)]
+    return dynamic_mix.DeviceCorpus(waves, list(range(len(waves))), "cuda")
+
+
+def time_dmix(corpus, M, C, T, steps, speeds=None):
+    mixer = dynamic_mix.DynamicMixer(corpus, M, C, T, speeds=speeds)
     for step in range(10):
         mixer.batch(step)
     windows = []
@@ -83,7 +95,7 @@ def time_dmix(json_dir, M, C, T, steps):
             mixer.batch(10 + w * steps + step)
         torch.cuda.synchronize()
         windows.append(1e3 * (time.perf_counter() - t0) / steps)
-    return statistics.median(windows), windows, corpus
+    return statistics.median(windows), windows
 
 
 def main():
@@ -95,6 +107,7 @@ def main():
     ap.add_argument("--batches", type=int, default=320, help="minibatches per host-loader pass")
     ap.add_argument("--steps", type=int, default=2000, help="DynamicMixer batches per timed window")
     ap.add_argument("--workers", type=int, nargs="*", default=[0, 4, 16])
+    ap.add_argument("--speeds", type=int, nargs="+", default=[95, 100, 105], help="percents of the perturbed row")
     ap.add_argument("--no-step", action="store_true", help="skip the bench.py run")
     ap.add_argument("--host-only", action="store_true", help="time the host loader only (needs no GPU)")
     a = ap.parse_args()
@@ -104,8 +117,13 @@ def main():
         # the worker processes are forked before this process opens the GPU
         out["host_loader_ms"] = {str(w): time_host_loader(json_dir, a.M, a.T, w, a.batches) for w in a.workers}
         if not a.host_only:
-            out["dmix_ms"], out["dmix_ms_windows"], corpus = time_dmix(json_dir, a.M, a.C, a.T, a.steps)
+            corpus = dynamic_mix.DeviceCorpus.from_json_dir(json_dir, SR, speaker_of=lambda path, slot: (slot, path))
+            out["dmix_ms"], out["dmix_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps)
             out["corpus_bytes"], out["pool_dtype"] = corpus.nbytes, "int16" if corpus.pool_dtype == 0 else "fp32"
+            corpus = long_corpus(a.utts, a.C, a.T)
+            out["dmix_long_ms"], out["dmix_long_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps)
+            out["speeds"] = a.speeds
+            out["dmix_speed_ms"], out["dmix_speed_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps, a.speeds)
     if not (a.no_step or a.host_only):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
                            check=True, capture_output=True, text=True)
