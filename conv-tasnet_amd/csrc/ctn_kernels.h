@@ -1,5 +1,5 @@
 // Internal (C++) launcher interface between the kernel files and the C-ABI
-// layer (ctn_capi.hip).  Not part of the public ABI: see include/ctn.h.
+// layer (ctn_capi_*.hip).  Not part of the public ABI: see include/ctn.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -11,7 +11,7 @@ namespace ctn {
 
 enum DType { F32 = 0, BF16 = 1 };
 
-// The current device's error word (ctn_capi.hip: allocated and zeroed on first use, read by
+// The current device's error word (ctn_capi_core.hip: allocated and zeroed on first use, read by
 // ctn_device_status / ctn_tblock_reduce_grads).  Kernels whose waves hand tiles to each
 // other through LDS generation words set CTN_DEVERR_SPIN in it when a wait runs out.
 uint32_t* device_error_word();

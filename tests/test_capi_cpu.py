@@ -192,6 +192,97 @@ def test_tblock_plan_bench_shape_and_2gb_fallback(lib):
     assert _plan(lib, 1, **just_below)["pairA"] == "dual_ws"
 
 
+# (M, K, B, H, P, dilation)
+_TB_SHAPES = ((2, 3199, 256, 512, 3, 4), (32, 3199, 256, 512, 3, 128), (1, 100, 64, 128, 3, 1),
+              (3, 257, 128, 256, 5, 2), (656, 3199, 256, 512, 3, 1))
+_F_TILED, _F_FAST = "gemm1=rows,dw_fwd=lane,gemm2=rows", "gemm1=ws,dw_fwd=wave,gemm2=ws"
+_B_TILED = "pairA=rows+cols,dw_bwd=lane,n1bwd=ew,gx+dW1=rows+cols"
+_B_FAST = "pairA=dual_ws,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"
+# (norm, dtype, shape index) -> (workspace fwd, workspace bwd, partials, deferred workspace, plan fwd, plan bwd);
+# the recorded values were the same for causal 0 and 1
+_TB_RECORDED = {
+    (0, 0, 0): (8256, 54950664, 27678984, 27271696, _F_TILED, _B_TILED),
+    (0, 0, 1): (119040, 469082228, 48483956, 420598528, _F_TILED, _B_TILED),
+    (0, 0, 2): (528, 267520, 69888, 197640, _F_TILED, _B_TILED),
+    (0, 0, 3): (1168, 4017408, 1394432, 2623000, _F_TILED, _B_TILED),
+    (0, 0, 4): (2120448, 8644686384, 43194160, 8601492352, _F_TILED, _B_TILED),
+    (0, 1, 0): (628544, 61793544, 48126984, 13666576, _F_FAST, _B_FAST),
+    (0, 1, 1): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
+    (0, 1, 2): (33296, 169216, 69888, 99336, _F_TILED, _B_TILED),
+    (0, 1, 3): (132240, 2706688, 1394432, 1312280, _F_TILED, _B_TILED),
+    (0, 1, 4): (2644736, 4345000496, 43194160, 4301806464, _F_TILED, _B_TILED),
+    (1, 0, 0): (512256, 55556360, 27678984, 27877632, _F_TILED, _B_TILED),
+    (1, 0, 1): (8192256, 478793332, 48483956, 430309632, _F_TILED, _B_TILED),
+    (1, 0, 2): (4352, 272640, 69888, 203008, _F_TILED, _B_TILED),
+    (1, 0, 3): (55552, 4089600, 1394432, 2695424, _F_TILED, _B_TILED),
+    (1, 0, 4): (167936256, 8844089136, 43194160, 8800895232, _F_TILED, _B_TILED),
+    (1, 1, 0): (2265344, 62372872, 48126984, 14246144, _F_FAST, _B_FAST),
+    (1, 1, 1): (28377344, 285331060, 65261172, 220070144, _F_FAST, _B_FAST),
+    (1, 1, 2): (37120, 174336, 69888, 104704, _F_TILED, _B_TILED),
+    (1, 1, 3): (186624, 2778880, 1394432, 1384704, _F_TILED, _B_TILED),
+    (1, 1, 4): (168460544, 4544403248, 43194160, 4501209344, _F_TILED, _B_TILED),
+    (2, 0, 0): (215360, 55157256, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 0, 1): (3302144, 472205916, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 0, 2): (4880, 273408, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 0, 3): (25488, 4045312, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 0, 4): (67214592, 8709699632, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 1, 0): (739648, 41525768, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 1, 1): (3826432, 261966428, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 1, 2): (37648, 175104, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 1, 3): (156560, 2734592, 0, 0, "bn:rows", "bn:rows+cols"),
+    (2, 1, 4): (67738880, 4410013744, 0, 0, "bn:rows", "bn:rows+cols"),
+}
+# the bf16 gLN bench shape (shape index 1) under one A/B switch each
+_TB_RECORDED_ENV = {
+    ("CTN_GEMM_DUAL", "0"): (672000, 258805876, 48483956, 210322176, _F_FAST,
+                             "pairA=ws+cols,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"),
+    ("CTN_GEMM_DUAL", "3"): (672000, 292327540, 82038388, 210289408, _F_FAST,
+                             "pairA=dual_ws,dw_bwd=wave,n1bwd=ew,gx+dW1=dual"),
+    ("CTN_FUSE_N1", "0"): (672000, 275550324, 65261172, 210289408, _F_FAST,
+                           "pairA=dual_ws,dw_bwd=wave,n1bwd=ew,gx+dW1=rows+cols"),
+    ("CTN_DUAL_WS", "0"): (672000, 275583092, 65261172, 210322176, _F_FAST,
+                           "pairA=dual,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"),
+    ("CTN_DW_WAVE", "0"): (672000, 275550324, 65261172, 210289408, "gemm1=ws,dw_fwd=lane,gemm2=ws",
+                           "pairA=dual_ws,dw_bwd=lane,gx=ws_n1bwd,dW1=cols"),
+}
+
+
+def _tb_sizes_and_plans(lib, norm, causal, dtype, shape):
+    M, K, B, H, P, dil = shape
+    r = ctypes.byref(_desc(M=M, K=K, Kp=lib.ctn_padded_frames(K), B=B, H=H, P=P, dilation=dil, causal=causal,
+                           norm_type=norm, dtype=dtype))
+    plans = []
+    for backward in (0, 1):
+        buf = ctypes.create_string_buffer(256)
+        assert lib.ctn_tblock_plan(r, backward, buf, 256) == 0
+        plans.append(buf.value.decode())
+    return (lib.ctn_tblock_workspace_bytes(r, 0), lib.ctn_tblock_workspace_bytes(r, 1),
+            lib.ctn_tblock_partials_bytes(r), lib.ctn_tblock_deferred_workspace_bytes(r), plans[0], plans[1])
+
+
+def test_tblock_sizes_and_plans_match_recorded(lib, monkeypatch):
+    """The TemporalBlock's workspace, partials and deferred-workspace byte counts and its
+    ctn_tblock_plan strings, for every norm, causality, dtype and a table of shapes, and for
+    the bf16 gLN bench shape under each A/B switch.  The expected values were recorded from
+    the library of the parent commit of the one that introduced the block plan (TbPlan,
+    ctn_capi_tblock.hip), on a machine without a device, where the depthwise segment sizing
+    assumes the MI355X's 256 CUs: a refactor of the host driver must leave every one of them
+    as it was."""
+    for var, _ in _TB_RECORDED_ENV:
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.delenv("CTN_WS_FOLD", raising=False)
+    monkeypatch.delenv("CTN_COLS_WS", raising=False)
+    for (norm, dtype, i), want in _TB_RECORDED.items():
+        for causal in (0, 1):
+            got = _tb_sizes_and_plans(lib, norm, causal, dtype, _TB_SHAPES[i])
+            assert got == want, (norm, causal, dtype, _TB_SHAPES[i], got)
+    for (var, val), want in _TB_RECORDED_ENV.items():
+        with monkeypatch.context() as mp:
+            mp.setenv(var, val)
+            got = _tb_sizes_and_plans(lib, 0, 0, 1, _TB_SHAPES[1])
+        assert got == want, (var, val, got)
+
+
 def test_pit_speaker_range(lib):
     """ctn_pit_workspace_bytes: 1..16 speakers (C <= 10 enumerated, 11..16 by assignment),
     0 bytes (unsupported) beyond."""

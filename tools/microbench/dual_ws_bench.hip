@@ -17,7 +17,7 @@
 
 using namespace ctn;
 
-// the library's device error word (ctn_capi.hip), here one word of this process
+// the library's device error word (ctn_capi_core.hip), here one word of this process
 uint32_t* ctn::device_error_word() {
   static uint32_t* w = nullptr;
   if (!w && hipMalloc(&w, 4) == hipSuccess) (void)hipMemset(w, 0, 4);
