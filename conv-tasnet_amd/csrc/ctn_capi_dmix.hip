@@ -1,6 +1,7 @@
 // C-ABI entries of dynamic mixing (include/ctn.h ctn_dmix_*).
 #include "ctn_capi_util.h"
 #include "ctn_dmix.h"
+#include "ctn_dmix_aug.h"
 
 using namespace ctn;
 
@@ -162,5 +163,132 @@ extern "C" int ctn_dmix_mix_sp(const ctn_dmix_desc* d, const ctn_dmix_speeds* sp
   a.M = d->M; a.C = d->C; a.T = d->T; a.level_mode = d->level_mode; a.peak = d->peak;
   a.gains = gains; a.sources = sources; a.mixture = mixture; a.status = status;
   CTN_HIP(launch_dmix_mix_sp(r, a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+// Reverberation and noise: ctn_dmix_draw_aug, ctn_dmix_mix_aug (ctn_dmix_aug.hip)
+static_assert(sizeof(ctn_dmix_aug) == 32, "ctn_dmix_aug layout");
+
+static int dmix_aug_check(const ctn_dmix_desc* d, const ctn_dmix_aug* g) {
+  if (!g) return fail(CTN_ERR_ARG, "null augmentation descriptor");
+  if (g->n_rirs < 0 || g->n_noise_utts < 0 || g->n_noise_elig < 0 || (g->n_noise_utts > 0) != (g->n_noise_elig > 0))
+    return fail(CTN_ERR_ARG, "bad augmentation descriptor n_rirs=%d n_noise_utts=%d n_noise_elig=%d", g->n_rirs,
+                g->n_noise_utts, g->n_noise_elig);
+  if (g->n_rirs > 0) {
+    if (!(g->rir_prob >= 0.f && g->rir_prob <= 1.f)) return fail(CTN_ERR_ARG, "rir_prob=%g outside [0, 1]", g->rir_prob);
+    if (g->rir_max_taps < 1) return fail(CTN_ERR_ARG, "rir_max_taps=%d (>= 1)", g->rir_max_taps);
+    if (g->rir_max_taps > DMIX_MAX_RIR_TAPS)
+      return fail(CTN_ERR_UNSUPPORTED, "rir_max_taps=%d > %d taps (limits)", g->rir_max_taps, DMIX_MAX_RIR_TAPS);
+  }
+  if (g->n_noise_utts > 0) {
+    if (g->noise_dtype != 0 && g->noise_dtype != 1) return fail(CTN_ERR_ARG, "noise_dtype=%d: 0 or 1", g->noise_dtype);
+    if (!isfinite(g->snr_lo_db) || !isfinite(g->snr_hi_db)) return fail(CTN_ERR_ARG, "snr_lo_db and snr_hi_db must be finite");
+    if (d->C + 1 > DMIX_MAX_C)
+      return fail(CTN_ERR_UNSUPPORTED, "C=%d with noise: C + 1 > %d slots per row (limits)", d->C, DMIX_MAX_C);
+  }
+  return CTN_OK;
+}
+
+// d, the optional speed table and the augmentation descriptor; fills the table's kernel form.
+static int dmix_aug_check_all(const ctn_dmix_desc* d, const ctn_dmix_speeds* sp, const ctn_dmix_aug* g,
+                              DmixSpeedTable* t) {
+  if (int rc = dmix_check(d)) return rc;
+  if (sp)
+    if (int rc = dmix_speeds_check(sp, d->T, t)) return rc;
+  return dmix_aug_check(d, g);
+}
+
+extern "C" size_t ctn_dmix_aug_workspace_bytes(const ctn_dmix_desc* d, const ctn_dmix_speeds* sp, const ctn_dmix_aug* g) {
+  DmixSpeedTable t{};
+  if (dmix_aug_check_all(d, sp, g, &t) != CTN_OK) return 0;
+  return dmix_aug_layout(d->M, d->C, d->T, sp != nullptr, g->n_rirs > 0, g->n_noise_utts > 0).bytes;
+}
+
+extern "C" int ctn_dmix_draw_aug(const ctn_dmix_desc* d, const ctn_dmix_speeds* sp, const ctn_dmix_aug* g,
+                                 const int64_t* off, const int32_t* spk, const int32_t* elig, const int64_t* noff,
+                                 const int32_t* nelig, int64_t first_sample, int64_t* first_sample_dev,
+                                 int64_t advance, ctn_dmix_entry* plan, int32_t* speed, int32_t* rir,
+                                 ctn_dmix_entry* nplan, void* stream) {
+  DmixSpeedTable t{};
+  if (int rc = dmix_aug_check_all(d, sp, g, &t)) return rc;
+  const bool noise = g->n_noise_utts > 0;
+  if (!off || !spk || !elig || !plan || (g->n_rirs > 0 && !rir) || (sp && !speed) || (noise && (!noff || !nelig || !nplan)))
+    return fail(CTN_ERR_ARG, "null pointer");
+  DmixAugDrawArgs x{};
+  x.M = d->M; x.C = d->C; x.T = d->T;
+  x.seed_lo = (uint32_t)d->seed; x.seed_hi = (uint32_t)(d->seed >> 32);
+  x.first = first_sample; x.first_dev = first_sample_dev;
+  x.n_rirs = g->n_rirs; x.rir_prob = g->rir_prob; x.rir = rir;
+  if (noise) {
+    x.NU = g->n_noise_utts; x.NE = g->n_noise_elig; x.noff = noff; x.nelig = nelig;
+    x.snr_lo = g->snr_lo_db; x.snr_hi = g->snr_hi_db;
+    x.nplan = reinterpret_cast<DmixEntry*>(nplan);
+  }
+  CTN_HIP(launch_dmix_draw_aug(x, (hipStream_t)stream));   // reads the device counter before it advances
+  DmixDrawArgs a = dmix_draw_args(d, off, spk, elig, first_sample, first_sample_dev, advance, plan);
+  if (sp) {
+    a.speed = speed; a.nspeed = t.n;
+    for (int k = 0; k < t.n; ++k) a.span[k] = t.s[k].span;
+  }
+  CTN_HIP(launch_dmix_draw(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+extern "C" int ctn_dmix_mix_aug(const ctn_dmix_desc* d, const ctn_dmix_speeds* sp, const ctn_dmix_aug* g,
+                                const float* filt, const void* pool, const int64_t* off, const ctn_dmix_entry* plan,
+                                const int32_t* speed, const float* rir_pool, const int64_t* roff, const int32_t* rir,
+                                const void* noise_pool, const int64_t* noff, const ctn_dmix_entry* nplan, float* gains,
+                                float* ngain, float* sources, float* mixture, float* noise_out, int32_t* status,
+                                void* ws, size_t ws_bytes, void* stream) {
+  DmixResampleArgs r{};
+  if (int rc = dmix_aug_check_all(d, sp, g, &r.sp)) return rc;
+  const bool rirs = g->n_rirs > 0, noise = g->n_noise_utts > 0;
+  if (!pool || !off || !plan || !gains || !sources || !mixture || !status || (sp && !speed) ||
+      (rirs && (!rir_pool || !roff || !rir)) || (noise && (!noise_pool || !noff || !nplan || !ngain)))
+    return fail(CTN_ERR_ARG, "null pointer");
+  if (sp && !filt && ctn_dmix_sp_filter_floats(sp) > 0) return fail(CTN_ERR_ARG, "null pointer (filter table)");
+  if ((uintptr_t)pool % (d->pool_dtype == 0 ? 2 : 4) || (uintptr_t)sources % 4 || (uintptr_t)mixture % 4 ||
+      (uintptr_t)filt % 4 || (uintptr_t)rir_pool % 4 || (uintptr_t)noise_out % 4 ||
+      (noise && (uintptr_t)noise_pool % (g->noise_dtype == 0 ? 2 : 4)))
+    return fail(CTN_ERR_ARG, "a pool, the filter table, sources, mixture or noise_out is not aligned to its element size");
+  if ((uintptr_t)roff % 8 || (uintptr_t)noff % 8 || (uintptr_t)off % 8)
+    return fail(CTN_ERR_ARG, "an offset table is not aligned to 8 bytes");
+  const DmixAugLayout L = dmix_aug_layout(d->M, d->C, d->T, sp != nullptr, rirs, noise);
+  if (!ws || ws_bytes < L.bytes) return fail(CTN_ERR_WORKSPACE, "workspace %zu < %zu", ws_bytes, L.bytes);
+  if ((uintptr_t)ws % 16) return fail(CTN_ERR_ARG, "workspace is not 16-byte aligned");
+  hipStream_t s = (hipStream_t)stream;
+  DmixMixArgs a{};
+  a.M = d->M; a.C = d->C; a.T = d->T; a.U = d->n_utts; a.pool_dtype = d->pool_dtype; a.level_mode = d->level_mode;
+  a.peak = d->peak;
+  a.pool = pool; a.off = off; a.plan = reinterpret_cast<const DmixEntry*>(plan);
+  a.gains = gains; a.sources = sources; a.mixture = mixture; a.status = status;
+  a.ws = reinterpret_cast<char*>(ws);
+  a.L = L.sp.mix;
+  if (sp) {
+    r.L = L.sp;
+    r.M = d->M; r.C = d->C; r.T = d->T; r.U = d->n_utts; r.pool_dtype = d->pool_dtype;
+    r.filt = filt; r.pool = pool; r.off = off; r.plan = a.plan; r.speed = speed;
+    r.ws = a.ws;
+    CTN_HIP(launch_dmix_resample(r, &a, s));
+  }
+  if (rirs) {
+    DmixReverbArgs v{};
+    v.M = d->M; v.C = d->C; v.T = d->T; v.U = a.U; v.pool_dtype = a.pool_dtype;
+    v.pool = a.pool; v.off = a.off; v.plan = a.plan;
+    v.n_rirs = g->n_rirs; v.max_taps = g->rir_max_taps;
+    v.rir_pool = rir_pool; v.roff = roff; v.rir = rir;
+    v.ws = a.ws; v.L = L;
+    CTN_HIP(launch_dmix_reverb(v, &a, s));
+  }
+  if (!noise) {
+    CTN_HIP(launch_dmix_mix(a, s));
+    return CTN_OK;
+  }
+  DmixNoiseArgs nz{};
+  nz.NU = g->n_noise_utts; nz.dtype = g->noise_dtype;
+  nz.pool = noise_pool; nz.off = noff; nz.nplan = reinterpret_cast<const DmixEntry*>(nplan);
+  nz.ngain = ngain; nz.noise_out = noise_out;
+  nz.off_pw = L.off_pw; nz.off_ng0 = L.off_ng0;
+  CTN_HIP(launch_dmix_mix_noise(a, nz, s));
   return CTN_OK;
 }

@@ -104,5 +104,9 @@ hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s);
 hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s);
 // a.plan, a.off, a.pool, a.U, a.pool_dtype of `mix` are replaced by the resampled pool's.
 hipError_t launch_dmix_mix_sp(const DmixResampleArgs& r, DmixMixArgs mix, hipStream_t s);
+// The stages that ctn_dmix_aug.hip composes: status and the gains before the guard (ssq + gain0),
+// and the resampler alone, which points `mix` at the resampled pool as launch_dmix_mix_sp does.
+hipError_t launch_dmix_gain0(const DmixMixArgs& a, hipStream_t s);
+hipError_t launch_dmix_resample(const DmixResampleArgs& r, DmixMixArgs* mix, hipStream_t s);
 
 }  // namespace ctn

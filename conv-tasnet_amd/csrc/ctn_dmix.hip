@@ -14,6 +14,7 @@
 // alignment: the 16-byte accesses are declared with that alignment (global memory on
 // gfx950 is accessed in unaligned mode) and cover exactly the thread's 8 samples, never a
 // byte outside the segment or the row; a last partial group of 8 goes sample by sample.
+// The device helpers shared with ctn_dmix_aug.hip (reverberation and noise) are in ctn_dmix_dev.h.
 // No atomics; every sum and max is finished in index order.  The exactness contract
 // (one rounding per source sample, the mixture an ordered fp32 sum of the stored sources)
 // needs every product and sum below to stay a separate operation:
@@ -21,6 +22,7 @@
 
 #include "ctn_common.h"
 #include "ctn_dmix.h"
+#include "ctn_dmix_dev.h"
 
 namespace ctn {
 
@@ -42,22 +44,6 @@ DmixLayout dmix_layout(int M, int C, int T) {
 // ---------------------------------------------------------------------------
 // draw
 // ---------------------------------------------------------------------------
-struct Philox { uint32_t r[4]; };
-CTN_DEV Philox philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-    k0 += 0x9E3779B9u;
-    k1 += 0xBB67AE85u;
-  }
-  return Philox{{c0, c1, c2, c3}};
-}
-
 // SP: the slot's speed index k = (r3 * S) >> 32 is drawn first and the segment needs span[k]
 // input samples instead of T (ctn_dmix_draw_sp); one entry of ratio 1/1 gives the plain plan.
 template <bool SP> __global__ __launch_bounds__(64) void dmix_draw_kernel(DmixDrawArgs a) {
@@ -111,70 +97,6 @@ hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s) {
 // ---------------------------------------------------------------------------
 // mix
 // ---------------------------------------------------------------------------
-typedef uint32_t v4u_a2 __attribute__((ext_vector_type(4), aligned(2)));
-typedef float v4f_a4 __attribute__((ext_vector_type(4), aligned(4)));
-
-// First pool sample of the entry's segment, or -1 for an entry that must not be read.
-CTN_DEV int64_t seg_base(const DmixMixArgs& a, const DmixEntry& e) {
-  if (e.utt < 0 || e.utt >= a.U || e.start < 0) return -1;
-  const int64_t o = a.off[e.utt], len = a.off[e.utt + 1] - o;
-  if ((int64_t)e.start + a.T > len) return -1;
-  return o + e.start;
-}
-
-// Samples [t0, t0 + 8) of the segment at pool sample `base` (exact in fp32); zeros past T.
-template <int DT> CTN_DEV void load8(const void* pool, int64_t base, int t0, int T, float x[8]) {
-  if (t0 + 8 <= T) {
-    if constexpr (DT == 0) {
-      const v4u_a2 v = *reinterpret_cast<const v4u_a2*>(reinterpret_cast<const int16_t*>(pool) + base + t0);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        x[2 * i] = (float)(int16_t)(v[i] & 0xffffu) * 0x1p-15f;
-        x[2 * i + 1] = (float)(int16_t)(v[i] >> 16) * 0x1p-15f;
-      }
-    } else {
-      const float* p = reinterpret_cast<const float*>(pool) + base + t0;
-      const v4f_a4 lo = *reinterpret_cast<const v4f_a4*>(p), hi = *reinterpret_cast<const v4f_a4*>(p + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        x[i] = lo[i];
-        x[4 + i] = hi[i];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      x[i] = 0.f;
-      if (t0 + i < T) {
-        if constexpr (DT == 0) x[i] = (float)reinterpret_cast<const int16_t*>(pool)[base + t0 + i] * 0x1p-15f;
-        else x[i] = reinterpret_cast<const float*>(pool)[base + t0 + i];
-      }
-    }
-  }
-}
-
-CTN_DEV void store8(float* row, int t0, int T, const float v[8]) {
-  if (t0 + 8 <= T) {
-    *reinterpret_cast<v4f_a4*>(row + t0) = v4f_a4{v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<v4f_a4*>(row + t0 + 4) = v4f_a4{v[4], v[5], v[6], v[7]};
-  } else {
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      if (t0 + i < T) row[t0 + i] = v[i];
-  }
-}
-
-// Block-wide fp32 max (a max has no rounding: any order gives the same bits); valid in thread 0.
-CTN_DEV float block_max(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) v = fmaxf(v, red[w]);
-  return v;
-}
-
 // grid: (m*C + c) * nchunk + chunk
 template <int DT> __global__ __launch_bounds__(256) void dmix_ssq_kernel(DmixMixArgs a) {
   __shared__ double red[4];
@@ -215,21 +137,6 @@ __global__ __launch_bounds__(64) void dmix_gain0_kernel(DmixMixArgs a) {
       g /= fmax(sqrt(s / (double)a.T), 1e-4);
     }
     g0[c] = (float)g;
-  }
-}
-
-// The row's unguarded mixture samples [t0, t0 + 8): the arithmetic of the final write.
-template <int DT> CTN_DEV void mix8(const DmixMixArgs& a, const int64_t* base, const float* g, int t0, float acc[8],
-                                    float* sources_row0) {
-  for (int c = 0; c < a.C; ++c) {
-    float x[8], v[8];
-    load8<DT>(a.pool, base[c], t0, a.T, x);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      v[i] = g[c] * x[i];
-      acc[i] = c == 0 ? v[i] : acc[i] + v[i];
-    }
-    if (sources_row0) store8(sources_row0 + (size_t)c * a.T, t0, a.T, v);
   }
 }
 
@@ -294,15 +201,21 @@ template <int DT> __global__ __launch_bounds__(256) void dmix_write_kernel(DmixM
   store8(mixrow, t0, a.T, acc);
 }
 
-hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s) {
-  const int nchunk = a.L.nchunk;
-  const dim3 blk(256), rows((unsigned)((long)a.M * nchunk)), segs((unsigned)((long)a.M * a.C * nchunk));
-  const bool i16 = a.pool_dtype == 0;
+hipError_t launch_dmix_gain0(const DmixMixArgs& a, hipStream_t s) {
+  const dim3 blk(256), segs((unsigned)((long)a.M * a.C * a.L.nchunk));
   if (a.level_mode == 1) {
-    if (i16) dmix_ssq_kernel<0><<<segs, blk, 0, s>>>(a);
+    if (a.pool_dtype == 0) dmix_ssq_kernel<0><<<segs, blk, 0, s>>>(a);
     else dmix_ssq_kernel<1><<<segs, blk, 0, s>>>(a);
   }
   dmix_gain0_kernel<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s) {
+  const int nchunk = a.L.nchunk;
+  const dim3 blk(256), rows((unsigned)((long)a.M * nchunk));
+  const bool i16 = a.pool_dtype == 0;
+  if (hipError_t e = launch_dmix_gain0(a, s); e != hipSuccess) return e;
   if (a.peak > 0.f) {
     if (i16) dmix_peak_kernel<0><<<rows, blk, 0, s>>>(a);
     else dmix_peak_kernel<1><<<rows, blk, 0, s>>>(a);
@@ -429,17 +342,22 @@ template <int DT> __global__ __launch_bounds__(256) void dmix_resample_kernel(Dm
   }
 }
 
-hipError_t launch_dmix_mix_sp(const DmixResampleArgs& r, DmixMixArgs mix, hipStream_t s) {
+hipError_t launch_dmix_resample(const DmixResampleArgs& r, DmixMixArgs* mix, hipStream_t s) {
   const unsigned segs = (unsigned)((long)r.M * r.C * r.L.mix.nchunk);
   if (r.pool_dtype == 0) dmix_resample_kernel<0><<<dim3(segs), dim3(256), 0, s>>>(r);
   else dmix_resample_kernel<1><<<dim3(segs), dim3(256), 0, s>>>(r);
-  mix.U = r.M * r.C;
-  mix.pool_dtype = 1;
-  mix.pool = r.ws + r.L.off_xr;
-  mix.off = reinterpret_cast<const int64_t*>(r.ws + r.L.off_off);
-  mix.plan = reinterpret_cast<const DmixEntry*>(r.ws + r.L.off_plan);
-  mix.ws = r.ws;
-  mix.L = r.L.mix;
+  mix->U = r.M * r.C;
+  mix->pool_dtype = 1;
+  mix->pool = r.ws + r.L.off_xr;
+  mix->off = reinterpret_cast<const int64_t*>(r.ws + r.L.off_off);
+  mix->plan = reinterpret_cast<const DmixEntry*>(r.ws + r.L.off_plan);
+  mix->ws = r.ws;
+  mix->L = r.L.mix;
+  return hipGetLastError();
+}
+
+hipError_t launch_dmix_mix_sp(const DmixResampleArgs& r, DmixMixArgs mix, hipStream_t s) {
+  if (hipError_t e = launch_dmix_resample(r, &mix, s); e != hipSuccess) return e;
   return launch_dmix_mix(mix, s);
 }
 

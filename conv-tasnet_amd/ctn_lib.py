@@ -93,6 +93,13 @@ class DmixSpeeds(ctypes.Structure):
     _fields_ = [("n", c_int32), ("r", DmixRatio * 8)]
 
 
+class DmixAug(ctypes.Structure):
+    """ctn_dmix_aug: reverberation and noise of ctn_dmix_draw_aug / ctn_dmix_mix_aug."""
+    _fields_ = [("n_rirs", c_int32), ("rir_max_taps", c_int32), ("rir_prob", ctypes.c_float),
+                ("n_noise_utts", c_int32), ("n_noise_elig", c_int32), ("noise_dtype", c_int32),
+                ("snr_lo_db", ctypes.c_float), ("snr_hi_db", ctypes.c_float)]
+
+
 MASK_IDENTITY = 2
 
 
@@ -172,6 +179,9 @@ _SIGS = {
     "ctn_dmix_draw_sp": (ctypes.c_int, [c_void_p] * 5 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
                                                          c_void_p]),
     "ctn_dmix_mix_sp": (ctypes.c_int, [c_void_p] * 11 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_dmix_aug_workspace_bytes": (c_size_t, [c_void_p] * 3),
+    "ctn_dmix_draw_aug": (ctypes.c_int, [c_void_p] * 8 + [ctypes.c_int64, c_void_p, ctypes.c_int64] + [c_void_p] * 5),
+    "ctn_dmix_mix_aug": (ctypes.c_int, [c_void_p] * 20 + [c_void_p, c_size_t, c_void_p]),
     "ctn_pack_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "ctn_opt_plan": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int]),
     "ctn_grad_clip_norm": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_float, c_void_p, c_void_p,

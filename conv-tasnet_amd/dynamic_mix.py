@@ -19,6 +19,11 @@ Speed perturbation (``DynamicMixer(..., speeds=(95, 100, 105))``
 source is resampled on the device by a polyphase FIR before it is mixed
 (ctn_dmix_draw_sp, ctn_dmix_mix_sp).  ``speed_ratio``, ``speed_filter``, ``segment_span``
 and ``resample_host`` restate it, and ``plan_host`` / ``mix_host`` take ``speeds``.
+
+Reverberation and noise (``DynamicMixer(..., rirs=RirBank(...), noise=corpus)``):
+every source is optionally convolved on the device with a drawn room impulse response and the
+mixture gets a drawn noise segment at a drawn SNR (ctn_dmix_draw_aug, ctn_dmix_mix_aug).
+``reverb_host``, ``plan_aug_host`` and ``mix_aug_host`` restate them.
 """
 from __future__ import annotations
 
@@ -219,6 +224,115 @@ def mix_host(pool, off, plan, T, level_mode=0, peak=0.9, gains=None, speeds=None
     return {"gains": g64, "p": p64, "sources": sources, "mixture": mixture, "status": status}
 
 
+MAX_RIR_TAPS = 16384
+_RIR_SLOT, _NOISE_SLOT = 16, 32                          # Philox counter word 2 of the RIR and noise draws
+
+
+def reverb_host(xs, h):
+    """The reverberated segment of ctn_dmix_mix_aug: xv[n] = sum_{j <= min(n, L - 1)} h[j] xs[n - j],
+    j upward, acc = fl32(acc + fl32(h[j] xs[n - j])) from +0; the segment starts from silence."""
+    xs, h = np.asarray(xs, np.float32), np.asarray(h, np.float32)
+    T = len(xs)
+    acc = np.zeros(T, np.float32)
+    for j in range(min(T, len(h))):
+        acc[j:] = acc[j:] + h[j] * xs[:T - j]            # fp32 product, one rounding; then the sum
+    return acc
+
+
+def plan_aug_host(off, spk, elig, M, C, T, seed=0, first_sample=0, level_db=(-2.5, 2.5), max_tries=16, speeds=None,
+                  n_rirs=0, rir_prob=1.0, noise_off=None, noise_elig=None, snr_db=(-5.0, 5.0)):
+    """What ctn_dmix_draw_aug writes -> dict(plan [M, C] PLAN_DTYPE, speed_idx [M, C] int32 (zeros
+    without speeds), rir [M, C] int32, nplan [M] PLAN_DTYPE or None without a noise pool)."""
+    src = plan_host(off, spk, elig, M, C, T, seed=seed, first_sample=first_sample, level_db=level_db,
+                    max_tries=max_tries, speeds=speeds)
+    plan, speed_idx = (src, np.zeros((M, C), np.int32)) if speeds is None else src
+    key = (int(seed) & _U32, (int(seed) >> 32) & _U32)
+    prob, two24 = np.float32(rir_prob), np.float32(2.0 ** -24)
+    rir = np.full((M, C), -1, np.int32)
+    nplan = None
+    if noise_off is not None:
+        noise_off, noise_elig = np.asarray(noise_off, np.int64), np.asarray(noise_elig, np.int32)
+        nplan = np.zeros(M, dtype=PLAN_DTYPE)
+        lo, hi = np.float32(snr_db[0]), np.float32(snr_db[1])
+    for m in range(M):
+        g = (int(first_sample) + m) & 0xFFFFFFFFFFFFFFFF
+        for c in range(C):
+            r = philox4x32_10((g & _U32, g >> 32, _RIR_SLOT + c, 0), key)
+            if n_rirs > 0 and np.float32(r[1] >> 8) * two24 < prob:
+                rir[m, c] = (r[0] * n_rirs) >> 32
+        if nplan is not None:
+            r = philox4x32_10((g & _U32, g >> 32, _NOISE_SLOT, 0), key)
+            utt = int(noise_elig[(r[0] * len(noise_elig)) >> 32])
+            snr = lo + (hi - lo) * (np.float32(r[2] >> 8) * two24)
+            n = int(noise_off[utt + 1] - noise_off[utt]) - T + 1 if 0 <= utt < len(noise_off) - 1 else 0
+            nplan[m] = (utt, (r[1] * n) >> 32, snr, 1) if 1 <= n <= 0x7FFFFFFF else (-1, 0, snr, 1)
+    return {"plan": plan, "speed_idx": speed_idx, "rir": rir, "nplan": nplan}
+
+
+def mix_aug_host(pool, off, plan, T, level_mode=0, peak=0.9, gains=None, ngain=None, speeds=None, speed_idx=None,
+                 rirs=None, rir=None, noise_pool=None, noise_off=None, nplan=None):
+    """ctn_dmix_mix_aug on the host.  rirs: list of fp32 tap arrays with rir [M, C] int32 (-1: dry);
+    noise_pool / noise_off / nplan [M] PLAN_DTYPE (level_db = snr_db): the noise stage.
+
+    -> dict(gains [M, C], ngain [M] float64: the gains in fp64 arithmetic; p [M] float64: the
+    unguarded mixture's peak; sources [M, C, T], mixture [M, T], noise [M, T] float32; status).
+    sources, mixture and noise follow the exactness contract with the fp32 `gains` / `ngain`
+    when given (a device call's read-back), else with the fp64 gains rounded to fp32."""
+    off = np.asarray(off, np.int64)
+    M, C = plan.shape
+    g64, n64, p64 = np.zeros((M, C)), np.zeros(M), np.zeros(M)
+    sources, mixture = np.zeros((M, C, T), np.float32), np.zeros((M, T), np.float32)
+    noise = np.zeros((M, T), np.float32)
+    status = np.zeros(M, np.int32)
+    ratios = None if speeds is None else _speed_table(speeds)
+    if ratios is not None and (speed_idx is None or np.shape(speed_idx) != (M, C)):
+        raise ValueError(f"speeds need speed_idx of shape {(M, C)}")
+    if rirs is not None and (rir is None or np.shape(rir) != (M, C)):
+        raise ValueError(f"rirs need rir of shape {(M, C)}")
+    if noise_pool is not None and (nplan is None or np.shape(nplan) != (M,)):
+        raise ValueError(f"a noise pool needs nplan of shape {(M,)}")
+    for m in range(M):
+        xs = [_segment(pool, off, plan[m, c], T, ratios, 0 if ratios is None else int(speed_idx[m, c]))
+              for c in range(C)]
+        z = None if noise_pool is None else _segment(noise_pool, np.asarray(noise_off, np.int64), nplan[m], T)
+        bad = any(x is None for x in xs) or (noise_pool is not None and z is None)
+        if rirs is not None:
+            ks = [int(k) for k in rir[m]]
+            bad = bad or any(not -1 <= k < len(rirs) or (k >= 0 and not 1 <= len(rirs[k]) <= MAX_RIR_TAPS) for k in ks)
+        if bad:
+            status[m] = 1
+            continue
+        if rirs is not None:
+            xs = [x if k < 0 else reverb_host(x, rirs[k]) for x, k in zip(xs, ks)]
+        for c, x in enumerate(xs):
+            g = 10.0 ** (float(plan[m, c]["level_db"]) / 20.0)
+            if level_mode == 1:
+                g /= max(float(np.sqrt(np.mean(x.astype(np.float64) ** 2))), 1e-4)
+            g64[m, c] = g
+        clean = sum(g64[m, c] * xs[c].astype(np.float64) for c in range(C))
+        if z is not None:
+            s = None                                     # the fp32 mixture before the guard, fp32 gains
+            for c, x in enumerate(xs):
+                v = np.float32(g64[m, c]) * x
+                s = v if s is None else s + v
+            ps, pz = np.mean(s.astype(np.float64) ** 2), np.mean(z.astype(np.float64) ** 2)
+            n64[m] = np.sqrt(ps / max(pz, 1e-8)) * 10.0 ** (-float(nplan[m]["level_db"]) / 20.0)
+            clean = clean + n64[m] * z.astype(np.float64)
+        p64[m] = np.abs(clean).max()
+        if peak > 0 and p64[m] > peak:
+            g64[m] *= peak / p64[m]
+            n64[m] *= peak / p64[m]
+        g32 = g64[m].astype(np.float32) if gains is None else np.asarray(gains, np.float32)[m]
+        for c, x in enumerate(xs):
+            sources[m, c] = g32[c] * x                     # one fp32 rounding per sample
+            mixture[m] = sources[m, c] if c == 0 else mixture[m] + sources[m, c]
+        if z is not None:
+            noise[m] = (np.float32(n64[m]) if ngain is None else np.asarray(ngain, np.float32)[m]) * z
+            mixture[m] = mixture[m] + noise[m]
+    return {"gains": g64, "ngain": n64, "p": p64, "sources": sources, "mixture": mixture, "noise": noise,
+            "status": status}
+
+
 # ----------------------------------------------------------------------------
 # device side
 # ----------------------------------------------------------------------------
@@ -309,6 +423,16 @@ class DeviceCorpus:
                 speakers.append(speaker_of(path, slot))
         return cls(waves, speakers, device)
 
+    @classmethod
+    def from_wav_dir(cls, wav_dir, sample_rate, device="cuda"):
+        """Every *.wav of wav_dir (sorted) as one utterance each, e.g. a noise pool; fp32 as
+        audio_io.read_wav returns, every file its own speaker."""
+        import audio_io
+        names = sorted(n for n in os.listdir(wav_dir) if n.lower().endswith(".wav"))
+        if not names:
+            raise ValueError(f"{wav_dir}: no wav files")
+        return cls([audio_io.read_wav(os.path.join(wav_dir, n), sr=sample_rate)[0] for n in names], names, device)
+
 
 def plan_to_numpy(plan):
     """Device plan tensor (int32 [M, C, 4]) -> [M, C] array of PLAN_DTYPE."""
@@ -322,6 +446,48 @@ def plan_from_numpy(plan, device):
     return torch.from_numpy(a.view(np.int32).reshape(a.shape[0], a.shape[1], 4).copy()).to(device)
 
 
+class RirBank:
+    """Room impulse responses resident in device memory, fp32 taps back to back.
+
+    rirs: arrays [L_i]; max_taps truncates the longer ones.  ValueError for an empty RIR or one of
+    more than 16384 taps (after truncation)."""
+
+    def __init__(self, rirs, device, max_taps=None):
+        import torch
+        rirs = [np.asarray(h, np.float32).reshape(-1) for h in rirs]
+        if max_taps is not None:
+            if int(max_taps) < 1:
+                raise ValueError(f"max_taps={max_taps}")
+            rirs = [h[:int(max_taps)] for h in rirs]
+        if len(rirs) == 0:
+            raise ValueError("no room impulse responses")
+        for i, h in enumerate(rirs):
+            if not 1 <= len(h) <= MAX_RIR_TAPS:
+                raise ValueError(f"room impulse response {i} has {len(h)} taps: 1 to {MAX_RIR_TAPS}")
+        self.rirs_host = rirs
+        self.roff_host = np.concatenate([[0], np.cumsum([len(h) for h in rirs])]).astype(np.int64)
+        self.max_len = max(len(h) for h in rirs)
+        self.device = torch.device(device)
+        self.pool = torch.from_numpy(np.concatenate(rirs)).to(self.device)
+        self.roff = torch.from_numpy(self.roff_host).to(self.device)
+
+    def __len__(self):
+        return len(self.rirs_host)
+
+    @classmethod
+    def from_dir(cls, rir_dir, sample_rate, max_taps=MAX_RIR_TAPS, device="cuda"):
+        """Every *.wav of rir_dir (sorted), mono through audio_io.read_wav at sample_rate;
+        `truncated` counts the files that had more than max_taps samples."""
+        import audio_io
+        names = sorted(n for n in os.listdir(rir_dir) if n.lower().endswith(".wav"))
+        if not names:
+            raise ValueError(f"{rir_dir}: no wav files")
+        rirs = [audio_io.read_wav(os.path.join(rir_dir, n), sr=sample_rate)[0] for n in names]
+        bank = cls(rirs, device, max_taps=max_taps)
+        bank.truncated = sum(len(h) > int(max_taps) for h in rirs)
+        return bank
+
+
 class DynamicMixer:
     """Draws and mixes batches of M rows, C speakers, T samples on the corpus's device.
 
@@ -331,10 +497,14 @@ class DynamicMixer:
     speeds: integer percents, e.g. (95, 100, 105): every source is played at one of them,
     drawn per slot, through the library's polyphase resampler (ctn_dmix_draw_sp,
     ctn_dmix_mix_sp; `.speed` holds the drawn indices).  None or all 100: no resampling, the
-    plain entry points."""
+    plain entry points.
+    rirs: a RirBank: every slot is convolved with one of its responses with probability rir_prob
+    (`.rir` holds the drawn indices, -1: dry).  noise: a DeviceCorpus: every row gets one of its
+    segments at an SNR drawn from snr_db = (lo, hi) (`.nplan`, `.ngain`).  Either one selects
+    ctn_dmix_draw_aug / ctn_dmix_mix_aug; both None: the entry points above."""
 
     def __init__(self, corpus, M, C, T, seed=0, level_mode=0, level_db=(-2.5, 2.5), peak=0.9, max_tries=16,
-                 rank=0, world=1, speeds=None):
+                 rank=0, world=1, speeds=None, rirs=None, rir_prob=1.0, noise=None, snr_db=(-5.0, 5.0)):
         import torch
 
         import ctn_lib as L
@@ -356,12 +526,34 @@ class DynamicMixer:
                                seed=int(seed) & 0xFFFFFFFFFFFFFFFF)
         self._lib = L.load()
         self.speed = self._filt = self._sp = None
-        if ratios is None:
-            nbytes = self._lib.ctn_dmix_workspace_bytes(ctypes.byref(self.desc))
-        else:
+        self.rirs, self.noise, self._aug = rirs, noise, None
+        self.rir = self.nplan = self.ngain = self.nelig = self.nelig_host = None
+        if ratios is not None:
             self._sp = L.DmixSpeeds(n=len(ratios))
             for k, (up, down) in enumerate(ratios):
                 self._sp.r[k].up, self._sp.r[k].down = up, down
+        if rirs is not None or noise is not None:
+            for what, other in (("rirs", rirs), ("noise", noise)):
+                if other is not None and other.pool.device != corpus.pool.device:
+                    raise ValueError(f"{what}: on {other.pool.device}, the corpus is on {corpus.pool.device}")
+            self._aug = L.DmixAug(rir_prob=float(rir_prob), snr_lo_db=float(snr_db[0]), snr_hi_db=float(snr_db[1]))
+            if rirs is not None:
+                self._aug.n_rirs, self._aug.rir_max_taps = len(rirs), rirs.max_len
+            if noise is not None:
+                if len(eligible(noise.off_host, self.T)) == 0:
+                    raise ValueError(f"noise: no recording holds the {self.T} samples of a segment")
+                self.nelig, self.nelig_host = noise.eligible(self.T, 0)
+                self._aug.n_noise_utts, self._aug.n_noise_elig = noise.n_utts, len(self.nelig_host)
+                self._aug.noise_dtype = noise.pool_dtype
+            nbytes = self._lib.ctn_dmix_aug_workspace_bytes(ctypes.byref(self.desc), self._sp_ref(),
+                                                            ctypes.byref(self._aug))
+            if nbytes == 0:                              # raises with the library's reason
+                L.check(self._lib.ctn_dmix_draw_aug(ctypes.byref(self.desc), self._sp_ref(), ctypes.byref(self._aug),
+                                                    None, None, None, None, None, 0, None, 0, None, None, None, None,
+                                                    None), "DynamicMixer")
+        elif ratios is None:
+            nbytes = self._lib.ctn_dmix_workspace_bytes(ctypes.byref(self.desc))
+        else:
             nbytes = self._lib.ctn_dmix_sp_workspace_bytes(ctypes.byref(self.desc), ctypes.byref(self._sp))
             if nbytes == 0:                              # raises with the library's reason
                 L.check(self._lib.ctn_dmix_draw_sp(ctypes.byref(self.desc), ctypes.byref(self._sp), None, None, None,
@@ -382,6 +574,14 @@ class DynamicMixer:
                                         f"{self._lib.ctn_dmix_sp_filter_floats(ctypes.byref(self._sp))}")
             self._filt = torch.from_numpy(taps).to(dev)
             self.speed = torch.zeros(self.M, self.C, dtype=torch.int32, device=dev)
+        if self._aug is not None:
+            self.rir = torch.full((self.M, self.C), -1, dtype=torch.int32, device=dev)
+            self.ngain = torch.zeros(self.M, dtype=torch.float32, device=dev)
+            if noise is not None:
+                self.nplan = torch.zeros(self.M, 1, 4, dtype=torch.int32, device=dev)
+
+    def _sp_ref(self):
+        return None if self._sp is None else ctypes.byref(self._sp)
 
     def first_sample(self, step):
         return (int(step) * self.world + self.rank) * self.M
@@ -403,6 +603,15 @@ class DynamicMixer:
         c = self.corpus
         if counter is not None:
             self._checked(counter, "counter", torch.int64, (1,))
+        if self._aug is not None:
+            n = self.noise
+            L.check(self._lib.ctn_dmix_draw_aug(ctypes.byref(self.desc), self._sp_ref(), ctypes.byref(self._aug),
+                                                L.ptr(c.off), L.ptr(c.spk), L.ptr(self.elig),
+                                                None if n is None else L.ptr(n.off), L.ptr(self.nelig),
+                                                int(first_sample), L.ptr(counter), int(advance), L.ptr(self.plan),
+                                                L.ptr(self.speed), L.ptr(self.rir), L.ptr(self.nplan),
+                                                L.stream_handle(c.device)), "ctn_dmix_draw_aug")
+            return self.plan
         if self.ratios is not None:
             L.check(self._lib.ctn_dmix_draw_sp(ctypes.byref(self.desc), ctypes.byref(self._sp), L.ptr(c.off),
                                                L.ptr(c.spk), L.ptr(self.elig), int(first_sample), L.ptr(counter),
@@ -414,9 +623,12 @@ class DynamicMixer:
                                         L.stream_handle(c.device)), "ctn_dmix_draw")
         return self.plan
 
-    def mix(self, plan=None, sources=None, mixture=None, speed=None):
+    def mix(self, plan=None, sources=None, mixture=None, speed=None, rir=None, nplan=None, noise_out=None):
         """Mix `plan` (default: the last drawn) -> (mixture [M, T], sources [M, C, T]).
-        speed: with speeds, the int32 [M, C] speed indices of `plan` (default: the last drawn)."""
+        speed: with speeds, the int32 [M, C] speed indices of `plan` (default: the last drawn).
+        rir: with rirs, the int32 [M, C] RIR indices (-1: dry); nplan: with noise, the int32
+        [M, 1, 4] noise plan (plan_from_numpy of [M, 1] entries); noise_out: with noise, a float32
+        [M, T] tensor that receives the scaled noise."""
         import torch
 
         import ctn_lib as L
@@ -433,6 +645,27 @@ class DynamicMixer:
             mixture = torch.empty(self.M, self.T, dtype=torch.float32, device=c.device)
         self._checked(sources, "sources", torch.float32, (self.M, self.C, self.T))
         self._checked(mixture, "mixture", torch.float32, (self.M, self.T))
+        if rir is not None:
+            if self.rirs is None:
+                raise ValueError("rir: this mixer was built without rirs")
+            self.rir = self._checked(rir, "rir", torch.int32, (self.M, self.C))
+        if nplan is not None or noise_out is not None:
+            if self.noise is None:
+                raise ValueError("nplan, noise_out: this mixer was built without noise")
+            if nplan is not None:
+                self.nplan = self._checked(nplan, "nplan", torch.int32, (self.M, 1, 4))
+            if noise_out is not None:
+                self._checked(noise_out, "noise_out", torch.float32, (self.M, self.T))
+        if self._aug is not None:
+            b, n = self.rirs, self.noise
+            L.check(self._lib.ctn_dmix_mix_aug(
+                ctypes.byref(self.desc), self._sp_ref(), ctypes.byref(self._aug), L.ptr(self._filt), L.ptr(c.pool),
+                L.ptr(c.off), L.ptr(self.plan), L.ptr(self.speed), None if b is None else L.ptr(b.pool),
+                None if b is None else L.ptr(b.roff), L.ptr(self.rir), None if n is None else L.ptr(n.pool),
+                None if n is None else L.ptr(n.off), L.ptr(self.nplan), L.ptr(self.gains), L.ptr(self.ngain),
+                L.ptr(sources), L.ptr(mixture), L.ptr(noise_out), L.ptr(self.status), L.ptr(self._ws),
+                self._ws.numel(), L.stream_handle(c.device)), "ctn_dmix_mix_aug")
+            return mixture, sources
         if self.ratios is not None:
             L.check(self._lib.ctn_dmix_mix_sp(ctypes.byref(self.desc), ctypes.byref(self._sp), L.ptr(self._filt),
                                               L.ptr(c.pool), L.ptr(c.off), L.ptr(self.plan), L.ptr(self.speed),

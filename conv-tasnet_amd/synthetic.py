@@ -30,3 +30,13 @@ def speech_like(M: int, C: int, T: int, seed: int):
             src[m, c] = y * 10 ** (rng.uniform(-2.5, 2.5) / 20)
     src_t = torch.from_numpy(src)
     return src_t.sum(1), src_t
+
+
+def synthetic_rir(n_taps: int, t60_s: float, sample_rate: int, seed: int):
+    """-> float32 [n_taps]: a unit direct tap followed by Gaussian noise whose amplitude falls by
+    60 dB in t60_s seconds (0.2 of the direct tap's level at the first sample)."""
+    rng = np.random.default_rng(seed)
+    t = np.arange(n_taps, dtype=np.float64) / float(sample_rate)
+    h = 0.2 * rng.standard_normal(n_taps) * 10.0 ** (-3.0 * t / float(t60_s))
+    h[0] = 1.0
+    return h.astype(np.float32)

@@ -21,7 +21,11 @@ Differences, each deliberate:
   training loader by dynamic_mix.DynamicMixLoader: batches drawn and mixed on the GPU from
   the s1..sC utterances of --train_dir (``--dm_*`` flags); cross validation is unchanged.
   ``--dm_speeds 95 100 105`` adds speed perturbation: each source is resampled on the GPU to
-  one of these speeds before it is mixed.
+  one of these speeds before it is mixed.  ``--dm_rir_dir`` / ``--dm_noise_dir`` (directories
+  of wav files) add reverberation and noise on the GPU: every source is convolved with a drawn
+  room impulse response (probability ``--dm_rir_prob``; responses longer than
+  ``--dm_rir_max_taps`` are truncated) and every mixture gets a drawn noise segment at an SNR
+  from ``--dm_snr_db LO HI``.  Cross validation keeps the fixed set.
 """
 import argparse
 import os
@@ -135,6 +139,17 @@ parser.add_argument('--dm_steps', default=0, type=int,
 parser.add_argument('--dm_speeds', default=[100], type=int, nargs='+', metavar='PCT',
                     help='Speed perturbation: every source is played at one of these percents, drawn per source '
                          '(e.g. 95 100 105; at most 8; the default 100 is off)')
+parser.add_argument('--dm_rir_dir', default='', type=str,
+                    help='Directory of room impulse responses (wav): every source is convolved with a drawn one '
+                         '(default: off)')
+parser.add_argument('--dm_rir_prob', default=1.0, type=float,
+                    help='Probability that a source is reverberated')
+parser.add_argument('--dm_rir_max_taps', default=16384, type=int,
+                    help='Longer room impulse responses are truncated to this many taps (at most 16384)')
+parser.add_argument('--dm_noise_dir', default='', type=str,
+                    help='Directory of noise recordings (wav): every mixture gets a drawn segment (default: off)')
+parser.add_argument('--dm_snr_db', default=[-5.0, 5.0], type=float, nargs=2, metavar=('LO', 'HI'),
+                    help='Range of the uniform draw of the clean mixture to noise ratio (dB)')
 
 
 def check_dm_speeds(args):
@@ -148,16 +163,44 @@ def check_dm_speeds(args):
         raise ValueError(f"--dm_speeds: {e}") from None
 
 
+def check_dm_aug(args):
+    """--dm_rir_dir and --dm_noise_dir need --dynamic_mix 1; the ranges the library accepts."""
+    import math
+    from dynamic_mix import MAX_RIR_TAPS
+    for flag in ("dm_rir_dir", "dm_noise_dir"):
+        if getattr(args, flag) and not args.dynamic_mix:
+            raise ValueError(f"--{flag} augments the dynamically mixed batches: it needs --dynamic_mix 1")
+    if not 0.0 <= args.dm_rir_prob <= 1.0:
+        raise ValueError(f"--dm_rir_prob {args.dm_rir_prob}: a probability in [0, 1]")
+    if not 1 <= args.dm_rir_max_taps <= MAX_RIR_TAPS:
+        raise ValueError(f"--dm_rir_max_taps {args.dm_rir_max_taps}: 1 to {MAX_RIR_TAPS}")
+    if not all(math.isfinite(v) for v in args.dm_snr_db):
+        raise ValueError(f"--dm_snr_db {args.dm_snr_db}: finite values")
+
+
 def dynamic_mix_loader(args, static_loader, rank, world):
     """The training loader of --dynamic_mix 1 (cross validation keeps the fixed set)."""
     if not args.use_cuda:
         raise ValueError("--dynamic_mix 1 mixes on the GPU: it cannot be combined with --use_cuda 0")
-    from dynamic_mix import DeviceCorpus, DynamicMixer, DynamicMixLoader
-    corpus = DeviceCorpus.from_json_dir(args.train_dir, args.sample_rate,
-                                        device=torch.device("cuda", torch.cuda.current_device()))
+    from dynamic_mix import DeviceCorpus, DynamicMixer, DynamicMixLoader, RirBank
+    device = torch.device("cuda", torch.cuda.current_device())
+    corpus = DeviceCorpus.from_json_dir(args.train_dir, args.sample_rate, device=device)
+    rirs = noise = None
+    if args.dm_rir_dir:
+        rirs = RirBank.from_dir(args.dm_rir_dir, args.sample_rate, args.dm_rir_max_taps, device)
+        if rank == 0:
+            print("Dynamic mixing: {} room impulse responses, up to {} taps{}".format(
+                len(rirs), rirs.max_len,
+                "; {} truncated to {} taps".format(rirs.truncated, args.dm_rir_max_taps) if rirs.truncated else ""))
+    if args.dm_noise_dir:
+        noise = DeviceCorpus.from_wav_dir(args.dm_noise_dir, args.sample_rate, device)
+        if rank == 0:
+            print("Dynamic mixing: {} noise recordings ({:.1f} MB on the device)".format(noise.n_utts,
+                                                                                       noise.nbytes / 1e6))
     mixer = DynamicMixer(corpus, args.batch_size, args.C, int(args.segment * args.sample_rate), seed=args.dm_seed,
                          level_mode=args.dm_level_mode, level_db=tuple(args.dm_level_db), peak=args.dm_peak,
-                         rank=rank, world=world, speeds=args.dm_speeds)
+                         rank=rank, world=world, speeds=args.dm_speeds, rirs=rirs, rir_prob=args.dm_rir_prob,
+                         noise=noise, snr_db=tuple(args.dm_snr_db))
     steps = args.dm_steps if args.dm_steps > 0 else len(static_loader)
     if rank == 0:
         print("Dynamic mixing: {} utterances ({:.1f} MB on the device), {} steps per epoch".format(
@@ -190,6 +233,7 @@ class FlatDP(Single):
 
 def main(args):
     check_dm_speeds(args)
+    check_dm_aug(args)
     if args.dynamic_mix and not args.use_cuda:
         raise ValueError("--dynamic_mix 1 mixes on the GPU: it cannot be combined with --use_cuda 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))

@@ -355,6 +355,81 @@ int ctn_dmix_mix_sp(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds, const
                     float* mixture /*[M][T]*/, int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Dynamic mixing with reverberation and noise: every source is optionally convolved with a
+ * drawn room impulse response (RIR) and the mixture optionally gets a drawn noise segment at
+ * a drawn SNR.  Added without an ABI bump: callers probe for the symbol.  ctn_dmix_draw,
+ * ctn_dmix_mix, ctn_dmix_draw_sp and ctn_dmix_mix_sp are unchanged, and with n_rirs = 0 and
+ * n_noise_utts = 0 the entries below write their bits (speeds == NULL: the plain pair).
+ *
+ * RIRs (caller-owned device memory): `rir_pool`, fp32 taps of all RIRs back to back, `roff`
+ * [n_rirs + 1] int64 tap offsets; rir_max_taps is the longest of them, 1 ... 16384 (a RIR
+ * that is empty or longer makes its row invalid).  Noise: a second pool `noise_pool` of
+ * noise_dtype 0 (int16 PCM) or 1 (fp32) with `noff` [n_noise_utts + 1] and `nelig`
+ * [n_noise_elig], as the speech pool.  n_rirs = 0: no reverberation; n_noise_utts =
+ * n_noise_elig = 0: no noise; the arguments of a stage that is off may be NULL and its outputs
+ * (nplan, ngain, noise_out; rir is written as -1 when given) are not touched.
+ *
+ * Row m (global sample g), slot c:
+ * 1. xs[n], n = 0 ... T - 1: the segment ctn_dmix_mix reads, or with a speed table the
+ *    resampled segment xr of ctn_dmix_mix_sp.
+ * 2. rir[m][c] = k >= 0, taps h[0 ... L - 1] = rir_pool[roff[k] ...]:
+ *      xv[n] = sum_{j = 0}^{min(n, L - 1)} h[j] xs[n - j],
+ *    j running upward, each step acc = fl32(acc + fl32(h[j] xs[n - j])) from +0, no FMA
+ *    contraction.  The segment starts from silence: samples before `start` do not feed the
+ *    tail.  k = -1: xv = xs exactly.  k outside [-1, n_rirs): the row is invalid (zeros,
+ *    status[m] = 1, nothing dereferenced).  A RIR's neighbours in the pool are never read.
+ * 3. The gains before the guard are those of ctn_dmix_mix applied to xv (level_mode 1: the
+ *    RMS of xv).
+ * 4. Noise, nplan[m] = {utt, start, level_db = snr_db, tries}: z[n] the exact fp32 sample,
+ *    s[n] the fp32 left-to-right sum of fl32(g_c xv_c[n]), P_s = (1/T) sum (double)s[n]^2,
+ *    P_z likewise (fp64 per-chunk partial sums finished in index order),
+ *      g_z = fl32(sqrt(P_s / max(P_z, 1e-8)) * 10^(-snr_db / 20))   (fp64, rounded once).
+ *    An invalid noise entry (as a source entry: utt, start, start + T > len) makes the row
+ *    invalid.
+ * 5. peak > 0: p = max_n |fl32(s[n] + fl32(g_z z[n]))|; if p > peak every gain of the row,
+ *    g_z included, becomes fl32(g * fl32(peak / p)).
+ * 6. gains[m][c], ngain[m] are the gains applied; sources[m][c][n] = fl32(gains xv) (the
+ *    reverberant signals that are in the mixture); mixture[m][n] = the fp32 sum of the stored
+ *    sources left to right with fl32(ngain z[n]) added last; noise_out [M][T] (or NULL)
+ *    receives fl32(ngain z).  Outputs may sit at any 4-byte alignment.
+ *
+ * ctn_dmix_draw_aug writes plan (and speed, with a table) with the bits of ctn_dmix_draw(_sp)
+ * and, same key,
+ *   rir[m][c]: counter (g_lo, g_hi, 16 + c, 0); u = fl32(r1 >> 8) * 2^-24;
+ *              u < rir_prob (fp32) ? (r0 * n_rirs) >> 32 : -1     (n_rirs = 0: -1)
+ *   nplan[m] : counter (g_lo, g_hi, 32, 0); utt = nelig[(r0 * n_noise_elig) >> 32],
+ *              start = (r1 * (len - T + 1)) >> 32, snr_db = lo + (hi - lo) * (r2 >> 8) * 2^-24
+ *              (fp32), tries = 1; utt = -1 for a bad nelig entry or an utterance shorter than T.
+ * The device-counter form works as in ctn_dmix_draw.
+ * Limits: those of ctn_dmix_mix(_sp); 0 <= rir_prob <= 1; finite SNRs; with noise C <= 15
+ * (0 workspace bytes / an error code beyond).  No atomics; the only transcendentals are in
+ * the one-thread-per-row gain kernels.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n_rirs;           /* 0: no reverberation */
+  int32_t rir_max_taps;     /* the longest RIR of the pool, 1 ... 16384 */
+  float rir_prob;           /* a slot is reverberated with this probability */
+  int32_t n_noise_utts;     /* 0: no noise */
+  int32_t n_noise_elig;
+  int32_t noise_dtype;      /* 0 int16 PCM, 1 fp32 */
+  float snr_lo_db, snr_hi_db;
+} ctn_dmix_aug;
+size_t ctn_dmix_aug_workspace_bytes(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds /*or NULL*/,
+                                    const ctn_dmix_aug* aug);
+int ctn_dmix_draw_aug(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds /*or NULL*/, const ctn_dmix_aug* aug,
+                      const int64_t* off, const int32_t* spk, const int32_t* elig, const int64_t* noff,
+                      const int32_t* nelig, int64_t first_sample, int64_t* first_sample_dev, int64_t advance,
+                      ctn_dmix_entry* plan /*[M][C]*/, int32_t* speed /*[M][C], with speeds*/,
+                      int32_t* rir /*[M][C]*/, ctn_dmix_entry* nplan /*[M], with noise*/, void* stream);
+int ctn_dmix_mix_aug(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds /*or NULL*/, const ctn_dmix_aug* aug,
+                     const float* filt, const void* pool, const int64_t* off, const ctn_dmix_entry* plan,
+                     const int32_t* speed, const float* rir_pool, const int64_t* roff /*[n_rirs+1]*/,
+                     const int32_t* rir /*[M][C]*/, const void* noise_pool, const int64_t* noff,
+                     const ctn_dmix_entry* nplan /*[M]*/, float* gains /*[M][C]*/, float* ngain /*[M]*/,
+                     float* sources /*[M][C][T]*/, float* mixture /*[M][T]*/, float* noise_out /*[M][T] or NULL*/,
+                     int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
  * Parameter update: replaces torch.nn.utils.clip_grad_norm_(params, max_norm)
  * (src/solver.py:184-185) and torch.optim.Adam(params, lr, weight_decay=l2)
  * (src/train.py:129-133, stepped at src/solver.py:186) with one launch each

@@ -18,10 +18,17 @@ utterances, C speakers, T samples:
                    first minibatch, i.e. without the start of the worker processes).  The
                    copy to the device is not included.
   step_ms          bench.py's training step (a child process), for scale
+  --aug adds, on the long corpus: dmix_reverb_ms (every source through one of
+                   --rirs synthetic room impulse responses of --rir-taps taps), dmix_noise_ms (a
+                   noise segment per row from a synthetic pool), dmix_aug_speed_ms (both, with
+                   --speeds), and host_fftconvolve_ms: scipy.signal.fftconvolve of the same M * C
+                   segments with a response of --rir-taps taps on --fft-threads threads (an fft
+                   in fp64, not the library's exact-order direct sum: for scale only)
 
 and prints one JSON object.
 
     python tools/bench_dmix.py [--M 32 --C 2 --T 32000 --utts 256 --batches 320 --steps 2000] [--no-step | --host-only]
+                               [--aug [--rir-taps 4000 --rirs 16]] [--dmix-only]
 """
 import argparse
 import json
@@ -83,8 +90,32 @@ def long_corpus(utts, C, T):
     return dynamic_mix.DeviceCorpus(waves, list(range(len(waves))), "cuda")
 
 
-def time_dmix(corpus, M, C, T, steps, speeds=None):
-    mixer = dynamic_mix.DynamicMixer(corpus, M, C, T, speeds=speeds)
+def aug_pools(a):
+    """(RirBank of --rirs synthetic responses of --rir-taps taps, PCM16 noise corpus of 16 x 4 T)."""
+    rirs = [synthetic.synthetic_rir(a.rir_taps, 0.4, SR, seed) for seed in range(a.rirs)]
+    _, src = synthetic.speech_like(16, 1, 4 * a.T, 2)
+    pcm = (src[:, 0] * (0.5 * 32767.0 / float(src.abs().max()))).round().to(torch.int16).numpy()
+    return dynamic_mix.RirBank(rirs, "cuda"), dynamic_mix.DeviceCorpus(list(pcm), list(range(len(pcm))), "cuda")
+
+
+def time_host_fftconvolve(M, C, T, taps, threads):
+    from concurrent.futures import ThreadPoolExecutor
+
+    import numpy as np
+    from scipy.signal import fftconvolve
+    rng = np.random.default_rng(0)
+    x, h = rng.standard_normal((M * C, T)), synthetic.synthetic_rir(taps, 0.4, SR, 0).astype(np.float64)
+    runs = []
+    with ThreadPoolExecutor(threads) as pool:
+        for _ in range(5):
+            t0 = time.perf_counter()
+            list(pool.map(lambda row: fftconvolve(row, h)[:T], x))
+            runs.append(1e3 * (time.perf_counter() - t0))
+    return statistics.median(runs[1:])
+
+
+def time_dmix(corpus, M, C, T, steps, speeds=None, **aug):
+    mixer = dynamic_mix.DynamicMixer(corpus, M, C, T, speeds=speeds, **aug)
     for step in range(10):
         mixer.batch(step)
     windows = []
@@ -110,12 +141,21 @@ def main():
     ap.add_argument("--speeds", type=int, nargs="+", default=[95, 100, 105], help="percents of the perturbed row")
     ap.add_argument("--no-step", action="store_true", help="skip the bench.py run")
     ap.add_argument("--host-only", action="store_true", help="time the host loader only (needs no GPU)")
+    ap.add_argument("--dmix-only", action="store_true", help="time the device rows only (no host loader, no bench.py)")
+    ap.add_argument("--aug", action="store_true", help="add the reverberation and noise rows")
+    ap.add_argument("--rir-taps", type=int, default=4000, help="taps of the synthetic room impulse responses")
+    ap.add_argument("--rirs", type=int, default=16, help="room impulse responses in the bank")
+    ap.add_argument("--fft-threads", type=int, default=16, help="threads of the host fftconvolve figure")
     a = ap.parse_args()
     out ={"M": a.M, "C": a.C, "T": a.T, "utts": a.utts}
     with tempfile.TemporaryDirectory() as root:
         json_dir = write_corpus(root, a.utts, a.C, a.T)
         # the worker processes are forked before this process opens the GPU
-        out["host_loader_ms"] = {str(w): time_host_loader(json_dir, a.M, a.T, w, a.batches) for w in a.workers}
+        if not a.dmix_only:
+            out["host_loader_ms"] = {str(w): time_host_loader(json_dir, a.M, a.T, w, a.batches) for w in a.workers}
+        if a.aug:
+            out["rir_taps"], out["fft_threads"] = a.rir_taps, a.fft_threads
+            out["host_fftconvolve_ms"] = time_host_fftconvolve(a.M, a.C, a.T, a.rir_taps, a.fft_threads)
         if not a.host_only:
             corpus = dynamic_mix.DeviceCorpus.from_json_dir(json_dir, SR, speaker_of=lambda path, slot: (slot, path))
             out["dmix_ms"], out["dmix_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps)
@@ -124,7 +164,14 @@ def main():
             out["dmix_long_ms"], out["dmix_long_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps)
             out["speeds"] = a.speeds
             out["dmix_speed_ms"], out["dmix_speed_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps, a.speeds)
-    if not (a.no_step or a.host_only):
+            if a.aug:
+                bank, noise = aug_pools(a)
+                steps = max(a.steps // 4, 1)
+                out["dmix_reverb_ms"], out["dmix_reverb_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, steps, rirs=bank)
+                out["dmix_noise_ms"], out["dmix_noise_ms_windows"] = time_dmix(corpus, a.M, a.C, a.T, a.steps, noise=noise)
+                out["dmix_aug_speed_ms"], out["dmix_aug_speed_ms_windows"] = time_dmix(
+                    corpus, a.M, a.C, a.T, steps, a.speeds, rirs=bank, noise=noise)
+    if not (a.no_step or a.host_only or a.dmix_only):
         r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "20", "--warmup", "5"],
                            check=True, capture_output=True, text=True)
         out["step_ms"] = json.loads(r.stdout.strip().splitlines()[-1])["ms_per_step"]
