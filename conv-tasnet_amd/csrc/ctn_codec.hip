@@ -640,16 +640,27 @@ __global__ __launch_bounds__(256) void dec_bwd_mfma_kernel(CodecArgs a) {
         for (int c = 0; c < CM; ++c) srcv[c][i] = wf[i] * act[c];
         float gwe = 0.f, dot = 0.f, ga[CM];
 #pragma unroll
-        for (int c = 0; c < CM; ++c)
+        for (int c = 0; c < CM; ++c) {
+          ga[c] = 0.f;
           if (c < C) {
             gwe += gs[c][i] * act[c];
             ga[c] = gs[c][i] * wf[i];   // dL/d act_c
             dot += ga[c] * act[c];
           }
+        }
         gwv[i] = gwe;
+        // dL/dscore_c: identity passes dL/d act_c through.  Two independent overrides of a
+        // value that is defined for every mask type: the nested conditional on the (uniform)
+        // mask type that this replaces left the identity result unassigned in the generated
+        // code (tests/test_gpu_codec.py, every bf16 matrix-core case of test_int_exact).
 #pragma unroll
         for (int c = 0; c < CM; ++c)
-          if (c < C) go[c][i] = a.mask_type == 1 ? act[c] * (ga[c] - dot) : a.mask_type == 0 ? (s[c] > 0.f ? ga[c] : 0.f) : ga[c];
+          if (c < C) {
+            float g = ga[c];
+            if (a.mask_type == 0 && !(s[c] > 0.f)) g = 0.f;
+            if (a.mask_type == 1) g = act[c] * (ga[c] - dot);
+            go[c][i] = g;
+          }
       }
 #pragma unroll
       for (int c = 0; c < CM; ++c)
