@@ -56,14 +56,14 @@ build/ws_bench_stamp: tools/microbench/ws_bench.hip $(PKG)/csrc/ctn_gemm_ws.hip 
 
 .PHONY: microbench
 
-# wave-specialised pair-A dual GEMM vs gemm_dual_kernel: build/dual_ws_bench_<bits>
+# pair-A dual GEMM microbenchmark and its bound-finding variants: build/dual_ws_bench_<bits>
 DV_EXPS := 0 1 2 4 8 32 34 64 96
 dualws: $(patsubst %,build/dual_ws_bench_%,$(DV_EXPS)) build/dual_ws_bench_stamp
-build/dual_ws_bench_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
+build/dual_ws_bench_%: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(HDR)
 	@mkdir -p build
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_EXP=$* $< -o $@
 # phase-stamp build: build/dual_ws_bench_stamp
-build/dual_ws_bench_stamp: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(PKG)/csrc/ctn_gemm_dual.hip $(HDR)
+build/dual_ws_bench_stamp: tools/microbench/dual_ws_bench.hip $(PKG)/csrc/ctn_dual_ws.hip $(HDR)
 	@mkdir -p build
 	$(HIPCC) -O3 -std=c++17 --offload-arch=$(ARCH) -Iinclude $(DEVFLAGS) -DCTN_DV_STAMP=1 $< -o $@
 

@@ -86,9 +86,8 @@ GemmCols tb_cols1(const ctn_tblock_desc* d) {
   c.P = d->H; c.Q = d->B; c.lda = d->H; c.ldb = d->B;
   return c;
 }
-// The backward's two dual GEMMs (ctn_gemm_dual.hip), shapes and operand ops only:
-//   A: g_n2 = gy . W2 (norm-2 backward epilogue) + dW2 = gy^T . norm2(PReLU(d))
-//   B: gx = gh1 . W1 + gy                        + dW1 = gh1^T . x
+// The backward's dual GEMM (ctn_dual_ws.hip), shapes and operand ops only: pair A,
+//   g_n2 = gy . W2 (norm-2 backward epilogue) + dW2 = gy^T . norm2(PReLU(d))
 GemmDual tb_dualA(const ctn_tblock_desc* d) {
   GemmDual g{};
   g.g = Rows{d->M, d->K, d->Kp};
@@ -96,14 +95,6 @@ GemmDual tb_dualA(const ctn_tblock_desc* d) {
   g.lda = d->B; g.ldw = d->B; g.ldc = d->H; g.ldr = d->H; g.ldb = d->H;
   g.epi = EPI_NORM_BWD;
   g.bop.kind = OP_PRELU_NORM; g.bop.norm = d->norm_type;
-  return g;
-}
-GemmDual tb_dualB(const ctn_tblock_desc* d) {
-  GemmDual g{};
-  g.g = Rows{d->M, d->K, d->Kp};
-  g.Kred = d->H; g.Nout = d->B; g.norm = d->norm_type;
-  g.lda = d->H; g.ldw = d->H; g.ldc = d->B; g.ldr = d->B; g.ldb = d->B;
-  g.epi = EPI_RESID;
   return g;
 }
 
@@ -140,9 +131,9 @@ struct TbPlan {
   int parts1, parts2; // slab parts per group of g1 / dw_fwd
   // backward
   GemmRows ga, gbF, gbP;   // pair A's row GEMM; gx GEMM, fused (norm-1 backward operand) / plain
-  GemmDual duA, duB;
+  GemmDual duA;
   GemmCols c1, c2;         // dW1, dW2
-  bool dualA, dualB;       // a pair runs as one dual GEMM
+  bool dualA;              // pair A runs as one dual GEMM
   bool fused1;             // norm-1/PReLU-1 backward inside gbF; else norm1_bwd_kernel
   bool foldX;              // fused1, gLN: gbF folds the norm-1 sums itself (CTN_WS_FOLD bit 1)
   bool clnFoldA;           // cLN: the wave-item dw_bwd folds the dual's per-row partials itself
@@ -157,7 +148,6 @@ struct TbPlan {
   // copies.  Asked only there, so that a forward or backward call pays for no query it does
   // not act on.
   const char* rows_kernel(const GemmRows& g) const { return gemm_ws_eligible(dt, g) ? "ws" : "rows"; }
-  const char* dual_kernel() const { return gemm_dual_ws_eligible(duA) ? "dual_ws" : "dual"; }
   const char* cols_kernel(const GemmCols& c) const { return gemm_cols_ws_eligible(dt, c) ? "cols_ws" : "cols"; }
   const char* dw_kernel(bool bwd) const { return dw_wave_eligible(dt, bwd ? dwB : dwF) ? "wave" : "lane"; }
 };
@@ -195,7 +185,6 @@ TbPlan tb_plan(const ctn_tblock_desc* d, bool backward) {
   pl.gbF = tb_gemm_out(d, nk, OP_NORM1_BWD);
   pl.gbP = tb_gemm_out(d, nk, OP_PLAIN);
   pl.duA = tb_dualA(d);
-  pl.duB = tb_dualB(d);
   pl.c1 = tb_cols1(d);
   pl.c2 = tb_cols2(d, nk);
   // Some eligibility functions of the kernel files also look at operand pointers, which a
@@ -205,13 +194,12 @@ TbPlan tb_plan(const ctn_tblock_desc* d, bool backward) {
   // the norm-1-backward operand of gbF must be present to be eligible; the launch always
   // supplies all of it, so the query below gets a stand-in for every pointer it tests.
   pl.dualA = gemm_dual_eligible(dt, pl.duA);
-  pl.dualB = gemm_dual_eligible(dt, pl.duB);
   // The norm-1/PReLU-1 backward runs inside the first 1x1's two gradient GEMMs (bf16,
-  // weight-stationary data-gradient kernel, dual pair B off); else norm1_bwd_kernel.
+  // weight-stationary data-gradient kernel); else norm1_bwd_kernel.
   // CTN_FUSE_N1=0 keeps the separate kernel (read on every call, so a process can compare
   // both paths: tests/test_gpu_tblock.py).
   const char* fuse = getenv("CTN_FUSE_N1");
-  if (!(fuse && atoi(fuse) == 0) && dt == BF16 && !pl.dualB) {
+  if (!(fuse && atoi(fuse) == 0) && dt == BF16) {
     static const float there[2] = {0.f, 0.f};
     GemmRows q = pl.gbF;
     q.aop.aux = there; q.aop.apart = const_cast<float*>(there); q.aop.aout = const_cast<float*>(there);
@@ -221,14 +209,14 @@ TbPlan tb_plan(const ctn_tblock_desc* d, bool backward) {
   pl.foldX = pl.fused1 && pl.fold && (ws_fold_mask() & 2);
   pl.partsD = dw_parts_per_group(pl.dwB);
   pl.chunks2 = pl.dualA ? gemm_dual_ranges(pl.duA) : gemm_cols_default_chunks(pl.c2);
-  pl.chunks1 = pl.dualB ? gemm_dual_ranges(pl.duB) : gemm_cols_chunks(dt, pl.c1);
+  pl.chunks1 = gemm_cols_chunks(dt, pl.c1);
   pl.dwb = dw_blocks(pl.dwB);
   pl.dws = dw_col_stride(pl.dwB);
   pl.ewb = ew_blocks(pl.dwB);
   pl.nalpha = pl.fused1 ? gemm_ws_grid(pl.gbF) : pl.ewb;
   // The norm-2 backward sums reach dw_bwd as pair A's partials.  gLN: always folded there.
   // cLN: the wave-item depthwise backward folds the dual's per-row partials itself (at most
-  // 4 per row: dual_ws_cln_parts_per_slice); otherwise a finalize launch makes them final.
+  // 4 per row: one per 128-channel slice); otherwise a finalize launch makes them final.
   if (pl.fold) {
     pl.f_sm2 = pl.dualA ? gemm_dual_stat_fold(pl.duA, nullptr, pl.cnt, 0.f, 1, nullptr)
                         : gemm_rows_stat_fold(dt, pl.ga, nullptr, pl.cnt, 0.f, 1, nullptr);
@@ -741,18 +729,11 @@ static int tb_backward(const ctn_tblock_desc* d, const ctn_tblock_params* p, con
     if (pl.fold) de.f_sm1 = StatFold{L.slabD, pl.partsD, pl.cnt, 0.f, 1, nullptr};
     CTN_HIP(launch_norm1_bwd(dt, de, s));
     // (e) gx = gh1 . W1 + gy
-    // (f) dW1 = gh1^T . x                          — one dual-GEMM pass when eligible
-    if (pl.dualB) {
-      GemmDual duB = pl.duB;
-      duB.A = L.G1; duB.W = w.w1; duB.Wf = w.w1f; duB.R = gy; duB.C = gx;
-      duB.Bm = x; duB.Dpart = L.cpart1;
-      CTN_HIP(launch_gemm_dual(duB, s));
-    } else {
-      GemmRows gb = pl.gbP;
-      gb.A = L.G1; gb.W = w.w1; gb.Wf = w.w1f; gb.R = gy; gb.C = gx;
-      CTN_HIP(launch_gemm_rows(dt, gb, s));
-      CTN_HIP(launch_gemm_cols(dt, c1, s));
-    }
+    // (f) dW1 = gh1^T . x
+    GemmRows gb = pl.gbP;
+    gb.A = L.G1; gb.W = w.w1; gb.Wf = w.w1f; gb.R = gy; gb.C = gx;
+    CTN_HIP(launch_gemm_rows(dt, gb, s));
+    CTN_HIP(launch_gemm_cols(dt, c1, s));
     if (sw != s) CTN_HIP(fork_stream(s, sw));
   }
   // (g) all parameter-gradient partial sums
@@ -792,12 +773,12 @@ extern "C" int ctn_tblock_plan(const ctn_tblock_desc* d, int backward, char* out
         ",gemm2=" + pl.rows_kernel(pl.g2);
   } else {
     const TbPlan pl = tb_plan(d, true);
-    s = std::string("pairA=") + (pl.dualA ? pl.dual_kernel() : pl.rows_kernel(pl.ga)) + (pl.dualA ? "" : "+cols") +
+    s = std::string("pairA=") + (pl.dualA ? "dual_ws" : pl.rows_kernel(pl.ga)) + (pl.dualA ? "" : "+cols") +
         ",dw_bwd=" + pl.dw_kernel(true);
     if (pl.fused1)
       s += std::string(",gx=ws_n1bwd,dW1=") + pl.cols_kernel(pl.c1);
     else
-      s += std::string(",n1bwd=ew,gx+dW1=") + (pl.dualB ? "dual" : "rows+cols");
+      s += ",n1bwd=ew,gx+dW1=rows+cols";
   }
   if (s.size() + 1 > cap) return fail(CTN_ERR_ARG, "plan needs %zu bytes", s.size() + 1);
   memcpy(out, s.c_str(), s.size() + 1);

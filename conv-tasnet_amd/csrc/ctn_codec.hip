@@ -15,9 +15,6 @@
 
 namespace ctn {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int EN_RPB = 128;   // frame rows per workgroup (matches the row padding)
 
 // ===========================================================================

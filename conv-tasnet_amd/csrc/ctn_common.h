@@ -94,6 +94,11 @@ CTN_DEV uint32_t pk_bf16(float a, float b) {
 CTN_DEV v4u pack_bf16x8v(const float f[8]) {
   return v4u{pk_bf16(f[0], f[1]), pk_bf16(f[2], f[3]), pk_bf16(f[4], f[5]), pk_bf16(f[6], f[7])};
 }
+// MFMA operand and accumulator fragments (v_mfma_f32_16x16x32_bf16), and the four bf16 of
+// one ds_read_b64_tr_b16
+typedef short bf16x8_t __attribute__((ext_vector_type(8)));
+typedef float f32x4_t __attribute__((ext_vector_type(4)));
+typedef short s16x4_t __attribute__((ext_vector_type(4)));
 
 // Workgroup barrier for LDS hand-offs only: waits for this wave's LDS operations
 // but NOT for its outstanding global loads/stores (__syncthreads()' release

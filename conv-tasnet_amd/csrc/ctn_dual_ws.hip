@@ -1,17 +1,51 @@
-// Wave-specialised dual GEMM, bf16, gfx950: the TemporalBlock backward's second 1x1
-// conv ("pair A", conv_tasnet.py:256-263 backward) in one pass over gy and d:
+// Dual GEMM, bf16, gfx950: a row GEMM and the weight gradient that shares its A stream,
+// in one pass over the frame rows.  It runs the TemporalBlock backward's second 1x1 conv
+// ("pair A", conv_tasnet.py:256-263 backward) in one pass over gy and d:
 //   C        = g_n2 = gy . W2                    (dL/d norm-2 output, stored bf16)
 //   grp_slab : norm-2 backward sums of (g_n2*gamma2, g_n2*gamma2*hat a2)
 //   Dpart    = gy^T . (gamma2 * hat a2 + beta2)  (dW2 partial per row range)
 // with hat a2 = (PReLU(d) - mean) * rstd (gLN per utterance or cLN per frame row).
-// Operands, outputs and partial layouts are those of gemm_dual_kernel's pair A
-// (ctn_gemm_dual.hip); C and Dpart are bit-identical to it (same MFMA sequences, same
-// operand transform), the statistics differ only by summation order.
+// Without the fusion these are two kernels (row GEMM + column GEMM), and gy and d stream
+// from HBM twice.
 //
-// Schedule.  gemm_dual_kernel runs every wave through one barrier per tile: wait for
-// the tile's LDS-DMA, then staging, MFMA and epilogue in lockstep, so the phases add
-// up.  Here the roles are split inside the workgroup (16 waves,
-// 4 per SIMD):
+// Operands (GemmDual, ctn_kernels.h; every matrix bf16, row-major, rows = M * Kp frame rows):
+//   A  = gy  [rows][lda], Kred = 256 channels; rows of padded frames (k >= K) read as zeros
+//   W  = W2^T [Nout][ldw]; Wf, when given, the same weight in MFMA fragment order
+//        (frag_offset: 1 KiB contiguous per wave and fragment)
+//   Bm = d   [rows][ldb], the raw pre-activation: the PReLU + norm + affine of the column
+//        operand and the PReLU + norm of the epilogue's hat a2 are both applied to it in
+//        registers (R is not read)
+//   stats = bop.stats: (mean, rstd) float2 per utterance [M] (gLN) or per frame row [rows]
+//        (cLN; padded frames' entries are not finite and are masked); gamma, bop.gamma,
+//        bop.beta [Nout] and alpha, bop.alpha [1] fp32
+// Outputs:
+//   C     [rows][ldc] bf16
+//   Dpart [range][Kred][Nout] fp32: one partial per row range, stored once per workgroup
+//         and summed over the ranges by slab_reduce in a fixed order
+//   grp_slab double2 (sum, sum of squares):
+//         gLN: [((range * S + slice) * DV_NR + row wave)][kmax], one entry per utterance
+//              run of the wave's tiles (the WsRuns layout of ctn_common.h, waves = S * DV_NR);
+//         cLN: [row][S], the four row waves' partials combined in LDS in the order 0..3.
+// Nothing is accumulated with atomics: every partial has one writer and every consumer
+// (slab_reduce, StatFold, stats_finalize) adds them in a fixed order, so all outputs are
+// bitwise reproducible.
+//
+// Decomposition.  The output channels are cut into S = Nout / 128 slices.  Workgroup
+// (row range, slice) keeps its slice of W resident in VGPRs (MFMA A-fragments, as the
+// weight-stationary kernel ctn_gemm_ws.hip) and its Dpart slice [256][128] as fp32 MFMA
+// accumulators, and streams the 32-row tiles of its range (the ranges split the tiles
+// evenly; 256 / S of them, or one per tile when there are fewer tiles).  Hardware
+// workgroup ids are dealt round-robin over the 8 XCDs, so when the grid is a multiple of
+// 8 S the S workgroups of one row range are given ids 8 apart and sit on the same XCD:
+// each gy tile is fetched from HBM once and re-read by the other slices from that XCD's L2.
+// Per tile the row part is v_mfma_f32_16x16x32_bf16 against the resident W slice with the
+// epilogue straight from the accumulators, and the column part is
+// Dpart += gy_tile^T . op(d)_tile with both operands read by ds_read_b64_tr_b16 (the
+// reduction runs over the tile's frame rows).
+//
+// Schedule.  A kernel that takes every wave through one barrier per tile (wait for the
+// tile's LDS-DMA, then staging, MFMA and epilogue in lockstep) makes the phases add up
+// (DESIGN.md §10-11).  Here the roles are split inside the workgroup (16 waves, 4 per SIMD):
 //   * 4 memory waves LDS-DMA the tiles PF tiles ahead into an LDS ring of NSL slots
 //     (A = gy in MFMA fragment order, B = raw d of the slice, the tile's statistics),
 //     wait for their own DMA with a counted vmcnt and publish FULL;
@@ -36,15 +70,17 @@ namespace ctn {
 
 namespace {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int DV_TM = 32;                        // frame rows per tile
 // 8 column waves (64 dW2 accumulators each, 4 waves per SIMD, 128 VGPRs per wave): 84 us
 // against 86-91 with 4 waves of 128 accumulators
 constexpr int DV_NR = 4, DV_NC = 8, DV_NMW = 4;  // row / column / memory waves
 constexpr int DV_ND = DV_NR + DV_NC;             // waves that publish DONE
+// The statistics partials follow from the row waves: gLN one run list per (range, slice,
+// row wave), cLN one entry per (row, slice) (the row waves' partials are combined in LDS).
+// Round 6 measured two other gLN forms, both bit-identical and slower, and removed them
+// (DESIGN.md §16): eight row waves with the tile DMA in the column waves (commit 9656623)
+// and the row epilogue in the memory waves (commit 9d56d29).
+constexpr int DV_CLN_PARTS = 1;                  // cLN statistics entries per (row, slice)
 constexpr int DV_NT = (DV_ND + DV_NMW) * 64;     // 1024 threads
 constexpr int DV_KB = 8, DV_KR = 256;            // reduction of the row part (gy channels)
 constexpr int DV_NS = 128;                       // output channels per slice
@@ -124,7 +160,7 @@ __device__ unsigned long long dv_stamps[1024 * 16 * 4];
 #endif
 
 // slot layout (bytes)
-constexpr int DV_A = DV_TM * DV_KR * 2;          // 16384: gy tile, WS fragment image (du_apiece)
+constexpr int DV_A = DV_TM * DV_KR * 2;          // 16384: gy tile, MFMA fragment-order image
 constexpr int DV_B = DV_TM * DV_NS * 2;          // raw d slice, 256-byte rows (dv_rbgr)
 constexpr int DV_ST = 256;                       // statistics
 constexpr int OFF_A = 0, OFF_B = OFF_A + DV_A, OFF_ST = OFF_B + DV_B;
@@ -438,8 +474,9 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
     for (int i = 0; i < CI; ++i)
 #pragma unroll
       for (int j = 0; j < CJ; ++j) dacc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-    // lane-constant LDS addresses (ctn_gemm_dual.hip's A addressing; B: row-major
-    // granules, block j at bbase ^ (j << 5))
+    // lane-constant LDS addresses (A: the fragment-order image, 16-row block mb and k-block
+    // kb of 1 KiB, 16-byte chunk lg at 256 lg, frame row r at 16 (r ^ (lg odd ? 12 : 0));
+    // B: row-major granules, block j at bbase ^ (j << 5))
     const int q = lr >> 2, pp = lr & 3;
     int abase[2], bbase[2];
 #pragma unroll
@@ -450,8 +487,9 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
       bbase[h] = dv_rbgr(row, 2 * CJ * wn + (pp >> 1)) + 8 * (pp & 1);
     }
     // the B fragment of block j holds raw d of column 16 (CJ wn + j) + lr (slice-local)
-    // at frame rows 8 lg .. 8 lg + 7; op(d) is applied here with gemm_dual_kernel's exact
-    // float operations (so C and Dpart match it bit for bit)
+    // at frame rows 8 lg .. 8 lg + 7; op(d) is applied here, per element in fp32:
+    // fma(PReLU(d) - mean, rstd * gamma2, beta2), rounded to bf16 (to nearest even); zero
+    // on cLN's padded frames
     float cg[CJ], cb[CJ];
 #pragma unroll
     for (int j = 0; j < CJ; ++j) {
@@ -678,41 +716,78 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// CTN_DUAL_WS=0 runs pair A on gemm_dual_kernel (ctn_gemm_dual.hip) instead; read on
-// every query, so one process can compare both.
-bool gemm_dual_ws_enabled() {
-  const char* e = getenv("CTN_DUAL_WS");
-  return e ? atoi(e) != 0 : true;
+// Row ranges of a launch over `rows` frame rows with `nout` sliced channels: the grid is
+// ranges * (nout / 128) workgroups
+static int dv_ranges(long rows, int nout) {
+  const long nt = rows / DV_TM;
+  const int want = DV_GRID / (nout / DV_NS);
+  return (int)(nt < want ? nt : want);
 }
 
-// cLN statistics entries per (row, slice) the kernel stores (gemm_dual_group_parts)
-int dual_ws_cln_parts_per_slice() { return 1; }
-
-// row waves per slice of the wave-specialised kernel (its gLN statistics partials are per
-// (range, slice, row wave): gemm_dual_runs).  Round 6 measured two other gLN forms, both
-// bit-identical and slower, and removed them: eight row waves with the
-// tile DMA in the column waves (commit 9656623) and the row epilogue in the memory waves
-// (commit 9d56d29).
-int dual_ws_row_waves(const GemmDual&) { return DV_NR; }
-
-bool gemm_dual_ws_eligible(const GemmDual& p) {
-  if (!gemm_dual_ws_enabled()) return false;
-  if (!(p.Kred == DV_KR && p.Nout % DV_NS == 0 && p.epi == EPI_NORM_BWD && p.bop.kind == OP_PRELU_NORM)) return false;
+// CTN_GEMM_DUAL bit 0 (default 1): pair A runs as this one kernel; cleared, as the row GEMM
+// + column GEMM kernels (109 us against 62 + 60 us at the time of the choice).
+// Every other bit is ignored.  Read on every query so a process can compare both paths
+// (tests/test_gpu_tblock.py).  Shapes that are not eligible take the two kernels as well.
+bool gemm_dual_eligible(DType dt, const GemmDual& p) {
+  const char* e = getenv("CTN_GEMM_DUAL");
+  if (dt != BF16 || (e && !(atoi(e) & 1))) return false;
+  // Only the paper's 256 -> 512 pair (S = 4 slices) takes the kernel: it is the one shape it is
+  // tested and measured at.  The kernel's own arithmetic would admit any Nout that is a multiple
+  // of 128 with 256 % S == 0; other widths run the row + column kernels.
+  if (!(p.Kred == DV_KR && p.Nout == 512 && p.epi == EPI_NORM_BWD && p.bop.kind == OP_PRELU_NORM)) return false;
   if (p.norm != NORM_GLN && p.norm != NORM_CLN) return false;
+  // one final statistics table serves the epilogue and the column operand
   if (p.bop.norm != p.norm || p.stats != p.bop.stats || p.bop.fold.slab) return false;
   if (p.g.Kp % DV_TM || p.lda % 8 || p.ldb % 8 || p.ldc % 8 || p.ldw % 8) return false;
   if (p.g.rows() / DV_TM < 1) return false;
-  // 32-bit tile offsets and buffer sizes (du_rsrc clamps at 2^31 bytes): larger tensors
-  // take the tiled kernels
+  // 32-bit tile offsets and buffer sizes (du_rsrc clamps at 2^31 bytes)
   if (p.g.rows() * (p.Kred > p.Nout ? p.Kred : p.Nout) * 2 >= (1L << 31)) return false;
-  const int S = p.Nout / DV_NS;
-  return DV_GRID % S == 0;
+  static_assert(512 % DV_NS == 0 && DV_GRID % (512 / DV_NS) == 0, "whole slices, whole row ranges");
+  return true;
 }
 
-int gemm_dual_ws_ranges(const GemmDual& p) {
-  const long nt = p.g.rows() / DV_TM;
-  const int want = DV_GRID / (p.Nout / DV_NS);
-  return (int)(nt < want ? nt : want);
+int gemm_dual_ranges(const GemmDual& p) { return dv_ranges(p.g.rows(), p.Nout); }
+
+// gLN: the run layout of the statistics partials (one run list per range, slice and row wave)
+static WsRuns gemm_dual_runs(const GemmDual& p) {
+  WsRuns w;
+  w.ntile = (int)(p.g.rows() / DV_TM);
+  w.grid = gemm_dual_ranges(p);
+  w.tpu = p.g.Kp / DV_TM;
+  w.waves = p.Nout / DV_NS * DV_NR;
+  w.kmax = ws_runs_kmax(w.ntile, w.grid, w.tpu);
+  return w;
+}
+
+int gemm_dual_group_parts(const GemmDual& p) {
+  if (p.norm != NORM_GLN) return p.Nout / DV_NS * DV_CLN_PARTS;
+  const WsRuns w = gemm_dual_runs(p);
+  const long entries = (long)w.grid * w.waves * w.kmax;
+  return (int)((entries + p.g.M - 1) / p.g.M);
+}
+
+StatFold gemm_dual_stat_fold(const GemmDual& p, const double2* slab, double cnt, float eps, int mode, float2* out) {
+  StatFold f;
+  f.slab = slab;
+  f.parts = gemm_dual_group_parts(p);
+  f.cnt = cnt;
+  f.eps = eps;
+  f.mode = mode;
+  f.out = out;
+  if (p.norm == NORM_GLN) f.ws = gemm_dual_runs(p);
+  return f;
+}
+
+hipError_t launch_gemm_dual(const GemmDual& pa, hipStream_t s) {
+  if (!gemm_dual_eligible(BF16, pa)) return hipErrorInvalidValue;
+  GemmDual p = pa;
+  p.err = device_error_word();
+  const dim3 grid(gemm_dual_ranges(p) * (p.Nout / DV_NS));
+  if (p.norm == NORM_GLN)
+    hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_GLN, DV_NSL, DV_PF>), grid, dim3(DV_NT), 0, s, p);
+  else
+    hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_CLN, DV_NSL, DV_PF>), grid, dim3(DV_NT), 0, s, p);
+  return hipGetLastError();
 }
 
 // The column GEMM alone (GemmCols, plain bf16 operands): dW[P][Q] partials per row range
@@ -733,11 +808,7 @@ bool gemm_cols_ws_eligible(DType dt, const GemmCols& c) {
   return true;
 }
 
-int gemm_cols_ws_ranges(const GemmCols& c) {
-  const long nt = c.g.rows() / DV_TM;
-  const int want = DV_GRID / (c.P / DV_NS);
-  return (int)(nt < want ? nt : want);
-}
+int gemm_cols_ws_ranges(const GemmCols& c) { return dv_ranges(c.g.rows(), c.P); }
 
 hipError_t launch_gemm_cols_ws(const GemmCols& c, hipStream_t s) {
   GemmDual p{};
@@ -751,18 +822,6 @@ hipError_t launch_gemm_cols_ws(const GemmCols& c, hipStream_t s) {
   const dim3 grid(gemm_cols_ws_ranges(c) * (c.P / DV_NS));
   hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_GLN, DV_NSL, DV_PF, true>), grid, dim3((DV_NC + DV_NMW) * 64), 0,
                      s, p);
-  return hipGetLastError();
-}
-
-hipError_t launch_gemm_dual_ws(const GemmDual& pa, hipStream_t s) {
-  if (!gemm_dual_ws_eligible(pa)) return hipErrorInvalidValue;
-  GemmDual p = pa;
-  p.err = device_error_word();
-  const dim3 grid(gemm_dual_ws_ranges(p) * (p.Nout / DV_NS));
-  if (p.norm == NORM_GLN)
-    hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_GLN, DV_NSL, DV_PF>), grid, dim3(DV_NT), 0, s, p);
-  else
-    hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_CLN, DV_NSL, DV_PF>), grid, dim3(DV_NT), 0, s, p);
   return hipGetLastError();
 }
 

@@ -21,10 +21,6 @@
 
 namespace ctn {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------------------
 // operand transform (applied per 16-byte chunk while staging)
 // ---------------------------------------------------------------------------

@@ -28,9 +28,6 @@
 
 namespace ctn {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
-
 constexpr int WS_WAVES = 8, WS_TM = 16, WS_GRID = 256;
 // Plain-operand configurations without a residual stream (the forward 1x1 conv, the
 // mask conv) take their tiles by LDS-DMA into a WS_DR-deep ring, handed off by one

@@ -98,9 +98,9 @@ struct GemmCols {
 int gemm_cols_default_chunks(const GemmCols& p);
 hipError_t launch_gemm_cols(DType dt, const GemmCols& p, hipStream_t s);
 
-// ---- dual GEMM (ctn_gemm_dual.hip): a row GEMM and the weight gradient that shares
-// its A stream, in one pass:  C[r][n] = sum_k A[r][k] W[n][k] (+ EPI_RESID / EPI_NORM_BWD
-// epilogue, fields as GemmRows) and Dpart[range][k][n] = sum_{r in range} A[r][k] op(Bm[r][n]).
+// ---- dual GEMM (ctn_dual_ws.hip): a row GEMM and the weight gradient that shares
+// its A stream, in one pass:  C[r][n] = sum_k A[r][k] W[n][k] (+ EPI_NORM_BWD epilogue,
+// fields as GemmRows) and Dpart[range][k][n] = sum_{r in range} A[r][k] op(Bm[r][n]).
 struct GemmDual {
   Rows g;
   int Kred, Nout;
@@ -123,16 +123,9 @@ struct GemmDual {
 bool gemm_dual_eligible(DType dt, const GemmDual& p);
 int gemm_dual_ranges(const GemmDual& p);
 int gemm_dual_group_parts(const GemmDual& p);
-int dual_ws_cln_parts_per_slice();   // ctn_dual_ws.hip: cLN statistics entries per (row, slice)
-int dual_ws_row_waves(const GemmDual& p);   // ctn_dual_ws.hip: row waves per slice (gLN partials)
 StatFold gemm_dual_stat_fold(const GemmDual& p, const double2* slab, double cnt, float eps, int mode,
                              float2* out);
 hipError_t launch_gemm_dual(const GemmDual& p, hipStream_t s);
-// wave-specialised pair-A kernel (ctn_dual_ws.hip), chosen by launch_gemm_dual
-bool gemm_dual_ws_enabled();
-bool gemm_dual_ws_eligible(const GemmDual& p);
-int gemm_dual_ws_ranges(const GemmDual& p);
-hipError_t launch_gemm_dual_ws(const GemmDual& p, hipStream_t s);
 // the same kernel's column part alone for plain bf16 column GEMMs (dW1 = gh1^T . x):
 // chosen by launch_gemm_cols when nchunks == gemm_cols_ws_ranges (gemm_cols_chunks)
 bool gemm_cols_ws_eligible(DType dt, const GemmCols& c);

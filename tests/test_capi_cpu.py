@@ -194,7 +194,10 @@ def test_tblock_plan_bench_shape_and_2gb_fallback(lib):
 
 # (M, K, B, H, P, dilation)
 _TB_SHAPES = ((2, 3199, 256, 512, 3, 4), (32, 3199, 256, 512, 3, 128), (1, 100, 64, 128, 3, 1),
-              (3, 257, 128, 256, 5, 2), (656, 3199, 256, 512, 3, 1))
+              (3, 257, 128, 256, 5, 2), (656, 3199, 256, 512, 3, 1),
+              # B = 256 with H != 512: pair A stays on the row + column kernels (the dual GEMM
+              # takes the 256 -> 512 pair only)
+              (32, 3199, 256, 256, 3, 4), (32, 3199, 256, 128, 3, 4))
 _F_TILED, _F_FAST = "gemm1=rows,dw_fwd=lane,gemm2=rows", "gemm1=ws,dw_fwd=wave,gemm2=ws"
 _B_TILED = "pairA=rows+cols,dw_bwd=lane,n1bwd=ew,gx+dW1=rows+cols"
 _B_FAST = "pairA=dual_ws,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"
@@ -231,17 +234,30 @@ _TB_RECORDED = {
     (2, 1, 2): (37648, 175104, 0, 0, "bn:rows", "bn:rows+cols"),
     (2, 1, 3): (156560, 2734592, 0, 0, "bn:rows", "bn:rows+cols"),
     (2, 1, 4): (67738880, 4410013744, 0, 0, "bn:rows", "bn:rows+cols"),
+    # recorded from the library of commit 8bcfc6c (the last with the tiled dual kernel)
+    (0, 0, 5): (64256, 247593044, 37293652, 210299648, _F_TILED, _B_TILED),
+    (0, 1, 5): (340736, 142487636, 37293652, 105194240, "gemm1=ws,dw_fwd=lane,gemm2=ws",
+                "pairA=ws+cols,dw_bwd=lane,gx=ws_n1bwd,dW1=cols"),
+    (1, 0, 5): (4915456, 254086740, 37293652, 216793344, _F_TILED, _B_TILED),
+    (1, 1, 5): (15008000, 158797396, 37293652, 121504000, "gemm1=ws,dw_fwd=lane,gemm2=ws",
+                "pairA=ws+cols,dw_bwd=lane,gx=ws_n1bwd,dW1=cols"),
+    (0, 0, 6): (32512, 140757584, 35605072, 105152768, _F_TILED, _B_TILED),
+    (0, 1, 6): (163584, 88197712, 35605072, 52592896, _F_TILED, _B_TILED),
+    (1, 0, 6): (3277056, 145640016, 35605072, 110035200, _F_TILED, _B_TILED),
+    (1, 1, 6): (3408128, 93080144, 35605072, 57475328, _F_TILED, _B_TILED),
 }
 # the bf16 gLN bench shape (shape index 1) under one A/B switch each
 _TB_RECORDED_ENV = {
     ("CTN_GEMM_DUAL", "0"): (672000, 258805876, 48483956, 210322176, _F_FAST,
                              "pairA=ws+cols,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"),
-    ("CTN_GEMM_DUAL", "3"): (672000, 292327540, 82038388, 210289408, _F_FAST,
-                             "pairA=dual_ws,dw_bwd=wave,n1bwd=ew,gx+dW1=dual"),
+    # only bit 0 of CTN_GEMM_DUAL is read (pair B's dual kernel is retired)
+    ("CTN_GEMM_DUAL", "2"): (672000, 258805876, 48483956, 210322176, _F_FAST,
+                             "pairA=ws+cols,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"),
+    ("CTN_GEMM_DUAL", "3"): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
     ("CTN_FUSE_N1", "0"): (672000, 275550324, 65261172, 210289408, _F_FAST,
                            "pairA=dual_ws,dw_bwd=wave,n1bwd=ew,gx+dW1=rows+cols"),
-    ("CTN_DUAL_WS", "0"): (672000, 275583092, 65261172, 210322176, _F_FAST,
-                           "pairA=dual,dw_bwd=wave,gx=ws_n1bwd,dW1=cols"),
+    # no longer read (the tiled dual kernel it selected is retired): the default plan
+    ("CTN_DUAL_WS", "0"): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
     ("CTN_DW_WAVE", "0"): (672000, 275550324, 65261172, 210289408, "gemm1=ws,dw_fwd=lane,gemm2=ws",
                            "pairA=dual_ws,dw_bwd=lane,gx=ws_n1bwd,dW1=cols"),
 }

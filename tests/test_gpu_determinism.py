@@ -7,9 +7,10 @@ twice on identical inputs at the c2 bench dispatch (gLN, M=32, K=3199) and at c4
 and parameter gradient must agree bitwise.  Every statistic and gradient partial is
 combined in a fixed order, so any difference is a race or a hardware
 hazard (the packed-FP32 op_sel hazard made the dual GEMM's norm-2
-statistics differ run to run).  The same is checked for the dual GEMM alone against the
-previous kernel (CTN_DUAL_WS=0) through the public block: C and dW2 are bit-identical by
-construction, the norm-2 sums agree to summation order.  GPU only.
+statistics differ run to run).  The dual GEMM is also compared with the row + column
+kernels it replaces (CTN_GEMM_DUAL=0) through the public block at the same dispatch: the
+two paths differ only in the summation order of the norm-2 sums and of the dW2 partials
+(DESIGN.md §22 has the measured differences).  GPU only.
 """
 import numpy as np
 import pytest
@@ -41,14 +42,17 @@ def test_block_bitwise_reproducible_at_bench_shapes(M, K, d, causal, norm):
 
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("norm,causal", [("gLN", 0), ("cLN", 1)])
-def test_wave_specialised_dual_matches_previous_kernel(norm, causal, monkeypatch):
-    """The block backward with the wave-specialised pair-A dual GEMM (default) against
-    the round-3 gemm_dual_kernel (CTN_DUAL_WS=0) at the bench dispatch: the same MFMA
-    sequences and operand transforms, so the data gradient and dW2 agree to the rounding
-    of the norm-2 sums' summation order (both deterministic)."""
+def test_dual_matches_row_and_column_kernels(norm, causal, monkeypatch):
+    """The block backward with the pair-A dual GEMM (default) against the row + column
+    kernels (CTN_GEMM_DUAL=0) at the bench dispatch: the same bf16 operands and per-element
+    transforms, so the data gradient and the parameter gradients agree to the rounding of
+    the norm-2 sums' and the dW2 partials' summation orders (both paths deterministic).
+    Measured at commit 8bcfc6c, the last with the tiled dual kernel: at most 2.5e-5 on gx
+    and 1.1e-5 on any parameter gradient, so the bounds of the comparison
+    with that kernel are kept."""
     outs = []
     for v in ("1", "0"):
-        monkeypatch.setenv("CTN_DUAL_WS", v)
+        monkeypatch.setenv("CTN_GEMM_DUAL", v)
         outs.append(_run(32, 3199, 4, causal, norm, 9))
     (y1, gx1, gp1), (y0, gx0, gp0) = outs
     assert torch.equal(y1, y0)

@@ -1,9 +1,8 @@
-// Pair-A dual GEMM at the paper shapes: the wave-specialised kernel (ctn_dual_ws.hip)
-// against gemm_dual_kernel (ctn_gemm_dual.hip) on the same inputs.
-//   * C and the dW2 partials bit for bit, the norm-2 statistics per group (sum of
-//     each kernel's partials) to 1e-9 relative;
-//   * run-to-run reproducibility of the wave-specialised kernel (every output byte);
-//   * time per launch (hipEvents over NIT launches).
+// Pair-A dual GEMM (ctn_dual_ws.hip) at the paper shapes:
+//   * run-to-run reproducibility (every byte of C and of the dW2 partials, and the norm-2
+//     statistics per group summed from the partials);
+//   * time per launch (hipEvents over NIT launches);
+//   * the per-role wait stamps (-DCTN_DV_STAMP=1) and the kernel's COLS mode.
 // Build with -DCTN_DV_EXP=<bits> for the bound-finding variants (timing only).
 // Usage: dual_ws_bench [M] [K] [g|c] [runs].  Not part of the library.
 #include <stdio.h>
@@ -13,7 +12,6 @@
 #include <vector>
 
 #include "../../conv-tasnet_amd/csrc/ctn_dual_ws.hip"
-#include "../../conv-tasnet_amd/csrc/ctn_gemm_dual.hip"
 
 using namespace ctn;
 
@@ -77,17 +75,15 @@ int main(int argc, char** argv) {
   const size_t nd = (size_t)gemm_dual_ranges(g) * B * H;
 
   struct Out { std::vector<uint16_t> c; std::vector<float> dp; std::vector<double> grp_s, grp_q; };
-  auto launch_once = [&](bool ws, Out* o) {
-    setenv("CTN_DUAL_WS", ws ? "1" : "0", 1);
+  auto launch_once = [&](Out* o) {
     CK(hipMemset(out, 0, cn * 2));
     CK(hipMemset(dpart, 0, nd * 4));
     CK(hipMemset(slab, 0, nslab * sizeof(double2)));
     CK(launch_gemm_dual(g, 0));
     CK(hipDeviceSynchronize());
-    if (!o) return;
     o->c = get<uint16_t>(out, cn);
     o->dp = get<float>(dpart, nd);
-    // per-group totals of the statistics partials, by each kernel's layout
+    // per-group totals of the statistics partials
     const int parts = gemm_dual_group_parts(g);
     const auto sl = get<double2>(slab, nslab);
     o->grp_s.assign(G, 0.0);
@@ -112,29 +108,13 @@ int main(int argc, char** argv) {
     }
   };
 
-  Out ref, cur;
-  launch_once(false, &ref);
-  launch_once(true, &cur);
-  long dc = 0, ddp = 0, dst = 0;
-  for (long i = 0; i < cn; ++i) dc += cur.c[i] != ref.c[i];
-  for (size_t i = 0; i < nd; ++i) ddp += memcmp(&cur.dp[i], &ref.dp[i], 4) != 0;
-  double worst = 0.0;
-  for (long i = 0; i < G; ++i) {
-    if (NK == NORM_CLN && i % Kp >= K) continue;
-    const double es = fabs(cur.grp_s[i] - ref.grp_s[i]) / (fabs(ref.grp_s[i]) + 1e-3);
-    const double eq = fabs(cur.grp_q[i] - ref.grp_q[i]) / (fabs(ref.grp_q[i]) + 1e-3);
-    const double e = es > eq ? es : eq;
-    if (e > 1e-6) ++dst;
-    if (e > worst) worst = e;
-  }
-  printf("M=%d K=%d %s  ws vs old: C %ld diffs, Dpart %ld diffs, stats %ld groups > 1e-6 (worst %.3g)\n", M, K,
-         NK == NORM_GLN ? "gLN" : "cLN", dc, ddp, dst, worst);
-
-  // run-to-run reproducibility of the wave-specialised kernel
+  // run-to-run reproducibility
+  Out cur;
+  launch_once(&cur);
   int bad = 0;
   for (int r = 0; r < NRUN; ++r) {
     Out o;
-    launch_once(true, &o);
+    launch_once(&o);
     long n = 0;
     for (long i = 0; i < cn; ++i) n += o.c[i] != cur.c[i];
     for (size_t i = 0; i < nd; ++i) n += memcmp(&o.dp[i], &cur.dp[i], 4) != 0;
@@ -147,8 +127,7 @@ int main(int argc, char** argv) {
   CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   const int NIT = 20;
   const double bytes = rows * (B + 2 * H) * 2.0;
-  for (int ws = 1; ws >= 0; --ws) {
-    setenv("CTN_DUAL_WS", ws ? "1" : "0", 1);
+  {
     for (int i = 0; i < 3; ++i) CK(launch_gemm_dual(g, 0));
     CK(hipDeviceSynchronize());
     CK(hipEventRecord(e0, 0));
@@ -157,18 +136,17 @@ int main(int argc, char** argv) {
     CK(hipEventSynchronize(e1));
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double us = ms * 1e3 / NIT;
-    printf("EXP %d %-4s M=%d K=%d %s %8.1f us  %7.0f GB/s (alg. bytes)\n", CTN_DV_EXP, ws ? "ws" : "old", M, K,
+    printf("EXP %d M=%d K=%d %s %8.1f us  %7.0f GB/s (alg. bytes)\n", CTN_DV_EXP, M, K,
            NK == NORM_GLN ? "gLN" : "cLN", us, bytes / us * 1e-3);
   }
 #if CTN_DV_STAMP
-  {   // per-role wait shares of the wave-specialised kernel (one more launch, stamps zeroed)
+  {   // per-role wait shares (one more launch, stamps zeroed)
     std::vector<unsigned long long> h(1024 * 16 * 4, 0ull);
     CK(hipMemcpyToSymbol(HIP_SYMBOL(dv_stamps), h.data(), h.size() * 8));
-    setenv("CTN_DUAL_WS", "1", 1);
     CK(launch_gemm_dual(g, 0));
     CK(hipDeviceSynchronize());
     CK(hipMemcpyFromSymbol(h.data(), HIP_SYMBOL(dv_stamps), h.size() * 8));
-    const int nwg = gemm_dual_ws_ranges(g) * (H / 128);
+    const int nwg = gemm_dual_ranges(g) * (H / 128);
     const char* role[3] = {"row", "column", "memory"};
     for (int r = 0; r < 3; ++r) {
       double acc[4] = {0, 0, 0, 0};
