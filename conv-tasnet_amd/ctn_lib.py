@@ -100,6 +100,11 @@ class DmixAug(ctypes.Structure):
                 ("snr_lo_db", ctypes.c_float), ("snr_hi_db", ctypes.c_float)]
 
 
+class StitchDesc(ctypes.Structure):
+    """ctn_stitch_desc (include/ctn.h): windowed separation, J windows of W samples."""
+    _fields_ = [(n, c_int32) for n in ("J", "C", "W", "O", "T")]
+
+
 MASK_IDENTITY = 2
 
 
@@ -182,6 +187,10 @@ _SIGS = {
     "ctn_dmix_aug_workspace_bytes": (c_size_t, [c_void_p] * 3),
     "ctn_dmix_draw_aug": (ctypes.c_int, [c_void_p] * 8 + [ctypes.c_int64, c_void_p, ctypes.c_int64] + [c_void_p] * 5),
     "ctn_dmix_mix_aug": (ctypes.c_int, [c_void_p] * 20 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_stitch_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_stitch_frame": (ctypes.c_int, [c_void_p] * 4),
+    "ctn_stitch_plan": (ctypes.c_int, [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_stitch_ola": (ctypes.c_int, [c_void_p] * 6),
     "ctn_pack_weights": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p]),
     "ctn_opt_plan": (ctypes.c_int, [c_void_p, ctypes.c_int, c_void_p, ctypes.c_int]),
     "ctn_grad_clip_norm": (ctypes.c_int, [c_void_p, c_void_p, ctypes.c_int, ctypes.c_float, c_void_p, c_void_p,

@@ -20,7 +20,10 @@ Same flags and printout as the reference.  Differences, each deliberate:
   this image, so SDRi parity is unpinned, DESIGN.md §4);
 * ``--sdr_device 1`` (default 0: nothing changes) computes SDRi of a whole minibatch on
   the device with that restatement's algorithm (``cal_SDRi_batch``, csrc/ctn_bss.hip,
-  DESIGN.md §18) instead of once per utterance on the host; same printout.
+  DESIGN.md §18) instead of once per utterance on the host; same printout;
+* ``--chunk_s SEC`` (default 0: nothing changes) separates every utterance in overlapping
+  windows of SEC seconds stitched on the device (``longform.ChunkedSeparator``, DESIGN.md
+  §23), so that the cost of windowing in SI-SNRi can be measured on a manifest.
 """
 import argparse
 
@@ -51,6 +54,10 @@ parser.add_argument('--pit_fix', default=0, type=int,
                     help='1: pair targets with the inverse of the best permutation (C >= 3)')
 parser.add_argument('--sdr_device', default=0, type=int,
                     help='1: with --cal_sdr 1, compute SDRi on the device (bss_eval, batched HIP kernels)')
+parser.add_argument('--chunk_s', default=0.0, type=float,
+                    help='Window in seconds for windowed separation (0: whole signal)')
+parser.add_argument('--chunk_overlap_s', default=None, type=float,
+                    help='Overlap of neighbouring windows in seconds (default: half of --chunk_s)')
 
 
 def reorder_inverse(est, source, lengths):
@@ -77,10 +84,25 @@ class Evaluator:
         dataset = AudioDataset(args.data_dir, args.batch_size, sample_rate=args.sample_rate, segment=-1)
         self.loader = AudioDataLoader(dataset, batch_size=1, num_workers=args.num_workers)
         self.records = []
+        from separate import make_chunker
+        self.chunker = make_chunker(self.model, getattr(args, 'chunk_s', 0.0), getattr(args, 'chunk_overlap_s', None),
+                                    args.sample_rate)
+
+    def _forward(self, mixture, lengths):
+        """[B, T] -> [B, C, T]: the whole-signal forward, or with --chunk_s each utterance
+        windowed at its own length (zeros past it, as the padded forward's tail is ignored)."""
+        if self.chunker is None:
+            return self.model(mixture)
+        from separate import chunked_estimates
+        ests = chunked_estimates(self.chunker, mixture, lengths)
+        out = mixture.new_zeros((mixture.size(0), ests[0].size(0), mixture.size(1)))
+        for b, e in enumerate(ests):
+            out[b, :, :e.size(1)] = e
+        return out
 
     def _separate(self, mixture, lengths, source):
         """-> estimates paired with the targets (the reference's reorder, or --pit_fix)."""
-        est = self.model(mixture)                                   # [B, C, T]
+        est = self._forward(mixture, lengths)                       # [B, C, T]
         _, _, est, paired = cal_loss(source, est, lengths)
         if self.args.pit_fix:
             paired = reorder_inverse(est, source, lengths)

@@ -14,6 +14,11 @@ The forward is the HIP path (``ConvTasNet`` on a ROCm device; the reference
 also requires a GPU, separate.py:44-46,64-66), in inference mode; wavs are
 written by audio_io (soundfile is not installed).  For frame-by-frame causal
 models see ``streaming.StreamingSeparator``.
+
+``--chunk_s SEC`` (default 0: off, nothing changes) separates each utterance, at its own
+length, in overlapping windows of SEC seconds that are stitched on the device
+(``longform.ChunkedSeparator``): memory does not grow with the recording
+and a gLN model is normalised over the length it was trained on.
 """
 import argparse
 import os
@@ -40,6 +45,10 @@ parser.add_argument('--sample_rate', default=8000, type=int,
                     help='Sample rate')
 parser.add_argument('--batch_size', default=1, type=int,
                     help='Batch size')
+parser.add_argument('--chunk_s', default=0.0, type=float,
+                    help='Window in seconds for windowed separation of long recordings (0: whole signal)')
+parser.add_argument('--chunk_overlap_s', default=None, type=float,
+                    help='Overlap of neighbouring windows in seconds (default: half of --chunk_s)')
 
 
 def output_stem(path: str) -> str:
@@ -50,17 +59,21 @@ def output_stem(path: str) -> str:
 class Separator:
     """A loaded model on the device plus the writer for its estimates."""
 
-    def __init__(self, model_path: str, sample_rate: int, device=None):
+    def __init__(self, model_path: str, sample_rate: int, device=None, chunk_s: float = 0.0, chunk_overlap_s=None):
         self.model = ConvTasNet.load_model(model_path)
         print(self.model)
         self.device = torch.device(device or "cuda")
         self.model.eval().to(self.device)
         self.sample_rate = sample_rate
+        self.chunker = make_chunker(self.model, chunk_s, chunk_overlap_s, sample_rate)
 
     @torch.no_grad()
     def estimate(self, mixture: torch.Tensor, lengths: torch.Tensor):
         """Padded mixtures [B, T] -> (trimmed mixtures, trimmed estimates [C, T_b]) per utterance."""
         mixture, lengths = mixture.to(self.device), lengths.to(self.device)
+        if self.chunker is not None:
+            return remove_pad(mixture, lengths), [e.cpu().numpy() for e in chunked_estimates(self.chunker, mixture,
+                                                                                               lengths)]
         est = self.model(mixture)
         return remove_pad(mixture, lengths), remove_pad(est, lengths)
 
@@ -78,11 +91,36 @@ class Separator:
                 self.save(out_dir, name, mix, est)
 
 
+def make_chunker(model, chunk_s, chunk_overlap_s, sample_rate):
+    """--chunk_s / --chunk_overlap_s -> a longform.ChunkedSeparator, or None when off.  Seconds
+    are rounded to the nearest window and overlap the model allows; the choice is printed."""
+    if not chunk_s or chunk_s <= 0:
+        return None
+    import longform
+    overlap_s = chunk_s / 2 if chunk_overlap_s is None else chunk_overlap_s
+    chunker = longform.from_seconds(model, chunk_s, overlap_s, sample_rate)
+    print("Windowed separation: window %d samples (%.4f s), overlap %d samples (%.4f s)" % (
+        chunker.window, chunker.window / sample_rate, chunker.overlap, chunker.overlap / sample_rate))
+    return chunker
+
+
+def chunked_estimates(chunker, mixture, lengths):
+    """Padded mixtures [B, T] -> device estimates [C, T_b], each utterance at its own length."""
+    ests = []
+    for b, n in enumerate(lengths.tolist()):
+        ests.append(chunker.separate(mixture[b, :n]))
+        for j in chunker.flagged():
+            print("Warning: utterance %d of the minibatch, window boundary %d: similarity not finite, "
+                  "speaker order kept" % (b, j))
+    return ests
+
+
 def separate(args):
     if args.mix_dir is None and args.mix_json is None:
         print("Must provide mix_dir or mix_json! When providing mix_dir, "
               "mix_json is ignored.")
-    sep = Separator(args.model_path, args.sample_rate)
+    sep = Separator(args.model_path, args.sample_rate, chunk_s=getattr(args, 'chunk_s', 0.0),
+                    chunk_overlap_s=getattr(args, 'chunk_overlap_s', None))
     dataset = EvalDataset(args.mix_dir, args.mix_json, batch_size=args.batch_size, sample_rate=args.sample_rate)
     sep.run(EvalDataLoader(dataset, batch_size=1), args.out_dir)
 

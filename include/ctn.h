@@ -430,6 +430,53 @@ int ctn_dmix_mix_aug(const ctn_dmix_desc* d, const ctn_dmix_speeds* speeds /*or 
                      int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Windowed separation of a recording of any length: the mixture x[T] is cut
+ * into J overlapping windows of W samples (overlap O, hop Hs = W - O), the model separates
+ * the windows as a batch, and the per-window outputs P [J][C][W] are joined on the device.
+ * Added without an ABI bump: callers probe for the symbol.
+ *
+ * J = 1 for T <= W, else 1 + ceil((T - W) / Hs); window j holds x[j Hs ... j Hs + W), zeros at
+ * and past T.  Limits: 2 <= C <= 8, 1 <= O <= W/2, T >= 1, T and W <= 2^30, and J as above; a
+ * violation, a null pointer or a workspace smaller than ctn_stitch_workspace_bytes() is
+ * CTN_ERR_ARG (0 workspace bytes), checked before anything is launched.
+ *
+ * ctn_stitch_frame writes the windows.
+ *
+ * ctn_stitch_plan, for every boundary j = 1 ... J-1:
+ *   S_j[a][b] = sum_{u < O} P[j-1][a][Hs + u] P[j][b][u]   in fp64 (sim[j], row-major), in
+ *   this order: chunk ch covers u in [2048 ch, 2048 ch + 2048); its thread t = 0 ... 255 adds,
+ *   from +0, the products at u = 2048 ch + 1024 h + 4 t + e for h = 0, 1 and e = 0 ... 3 in turn
+ *   (u >= O adds nothing); the 256 thread sums are added as v[l] += v[l + s], s = 32, 16, ..., 1
+ *   inside each group of 64, then ((w0 + w1) + w2) + w3 over the four groups; the chunk sums
+ *   are added from +0 in index order.
+ *   perm[j] = pi_j maximises sum_a S_j[a][pi_j(a)] (added a = 0 upward); the C! permutations
+ *   are taken in lexicographic order and a later one wins only when strictly greater.  If an
+ *   entry of S_j is not finite, pi_j is the identity and status[j] = 1 (else 0).
+ *   sigma[0] = identity, sigma[j][a] = pi_j(sigma[j-1][a]).  Row 0 of sim, perm and status is
+ *   zeros, the identity and 0.
+ *
+ * ctn_stitch_ola: out[a][t], t < T, with j = min(t / Hs, J - 1) and u = t - j Hs:
+ *   j >= 1 and u < O:  fl(fl(fl(1 - fade[u]) p) + fl(fade[u] c)),  p = P[j-1][sigma[j-1][a]][Hs + u],
+ *                      c = P[j][sigma[j][a]][u]   (fp32, each operation rounded, no contraction)
+ *   otherwise       :  P[j][sigma[j][a]][u]
+ * A sigma entry outside [0, C) reads channel a.  No atomics anywhere: the same bits every run.
+ * ------------------------------------------------------------------------- */
+typedef struct {
+  int32_t J;   /* windows */
+  int32_t C;   /* speakers */
+  int32_t W;   /* window, samples */
+  int32_t O;   /* overlap, samples */
+  int32_t T;   /* recording, samples */
+} ctn_stitch_desc;
+size_t ctn_stitch_workspace_bytes(const ctn_stitch_desc* d);
+int ctn_stitch_frame(const ctn_stitch_desc* d, const float* x /*[T]*/, float* win /*[J][W]*/, void* stream);
+int ctn_stitch_plan(const ctn_stitch_desc* d, const float* P /*[J][C][W]*/, double* sim /*[J][C][C]*/,
+                    int32_t* perm /*[J][C]*/, int32_t* sigma /*[J][C]*/, int32_t* status /*[J]*/, void* ws,
+                    size_t ws_bytes, void* stream);
+int ctn_stitch_ola(const ctn_stitch_desc* d, const float* P /*[J][C][W]*/, const int32_t* sigma /*[J][C]*/,
+                   const float* fade /*[O]*/, float* out /*[C][T]*/, void* stream);
+
+/* -------------------------------------------------------------------------
  * Parameter update: replaces torch.nn.utils.clip_grad_norm_(params, max_norm)
  * (src/solver.py:184-185) and torch.optim.Adam(params, lr, weight_decay=l2)
  * (src/train.py:129-133, stepped at src/solver.py:186) with one launch each
