@@ -70,7 +70,7 @@ EncLayout enc_layout(const ctn_codec_desc* d, int backward, void* ws) {
       L.Lp = (d->L + 7) & ~7;
       L.gpre_bf = c.take<void>((size_t)rows * d->N * 2);
       L.xfr = c.take<void>((size_t)rows * L.Lp * 2);
-      L.chunksU = gemm_cols_default_chunks(du_gemm(d, L.Lp));
+      L.chunksU = gemm_cols_chunks(du_gemm(d, L.Lp));
       L.cpartU = c.take<float>((size_t)L.chunksU * d->N * L.Lp * sizeof(float));
       L.tmpU = c.take<float>((size_t)d->N * L.Lp * sizeof(float));
     } else {
@@ -80,7 +80,7 @@ EncLayout enc_layout(const ctn_codec_desc* d, int backward, void* ws) {
     }
     GemmCols gc{};
     gc.g = Rows{d->M, d->K, d->Kp}; gc.P = d->B; gc.Q = d->N;
-    L.chunksB = gemm_cols_default_chunks(gc);
+    L.chunksB = gemm_cols_chunks(gc);
     L.cpartB = c.take<float>((size_t)L.chunksB * d->B * d->N * sizeof(float));
     const size_t ntmp = sr_tmp(L.chunksB, (long)d->B * d->N) + 2 * sr_tmp(L.rowblocks, d->N) +
                         sr_tmp(L.nU, (long)d->N * d->L) + sr_tmp(L.chunksU, (long)d->N * L.Lp);
@@ -228,7 +228,7 @@ DecLayout dec_layout(const ctn_codec_desc* d, int backward, bool with_mask_conv,
       L.Lp = (d->L + 7) & ~7;
       L.srcb = c.take<void>((size_t)rows * d->C * d->N * es);
       L.gfr = c.take<void>((size_t)rows * d->C * L.Lp * es);
-      L.chunksV = gemm_cols_default_chunks(dv_gemm(d, L.Lp));
+      L.chunksV = gemm_cols_chunks(dv_gemm(d, L.Lp));
       L.cpartV = c.take<float>((size_t)L.chunksV * L.Lp * d->N * sizeof(float));
     } else {
       L.nV = frame_outer_chunks(a, d->C);
@@ -239,7 +239,7 @@ DecLayout dec_layout(const ctn_codec_desc* d, int backward, bool with_mask_conv,
       L.gscore = c.take<void>((size_t)rows * CN * es);
       GemmCols gc{};
       gc.g = Rows{d->M, d->K, d->Kp}; gc.P = CN; gc.Q = d->B;
-      L.chunksM = gemm_cols_default_chunks(gc);
+      L.chunksM = gemm_cols_chunks(gc);
       L.cpartM = c.take<float>((size_t)L.chunksM * CN * d->B * sizeof(float));
     }
     L.srtmp = c.take<float>((sr_tmp(L.nV > L.chunksV ? L.nV : L.chunksV, (long)d->N * d->L) +

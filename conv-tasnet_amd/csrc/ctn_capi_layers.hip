@@ -174,7 +174,7 @@ C1Layout c1_layout(const ctn_rows_desc* d, int cout, int bwd, void* ws) {
     if (d->dtype == CTN_DTYPE_BF16) L.ws_w = c.take<void>((size_t)cout * d->C * es);
   } else {
     L.ws_wt = c.take<void>((size_t)cout * d->C * es);
-    L.chunks = gemm_cols_chunks(d->dtype == CTN_DTYPE_BF16 ? BF16 : F32, c1_cols(d, cout));
+    L.chunks = gemm_cols_chunks(c1_cols(d, cout));
     L.cpart = c.take<float>((size_t)L.chunks * cout * d->C * sizeof(float));
   }
   L.bytes = c.off + 256;

@@ -148,7 +148,6 @@ struct TbPlan {
   // copies.  Asked only there, so that a forward or backward call pays for no query it does
   // not act on.
   const char* rows_kernel(const GemmRows& g) const { return gemm_ws_eligible(dt, g) ? "ws" : "rows"; }
-  const char* cols_kernel(const GemmCols& c) const { return gemm_cols_ws_eligible(dt, c) ? "cols_ws" : "cols"; }
   const char* dw_kernel(bool bwd) const { return dw_wave_eligible(dt, bwd ? dwB : dwF) ? "wave" : "lane"; }
 };
 
@@ -189,10 +188,9 @@ TbPlan tb_plan(const ctn_tblock_desc* d, bool backward) {
   pl.c2 = tb_cols2(d, nk);
   // Some eligibility functions of the kernel files also look at operand pointers, which a
   // plan does not have.  Left null they answer as at the launch: pair A wants one statistics
-  // table for both of its uses (the launch passes st2 twice) and the column kernels want
-  // 16-byte alignment (the launch passes carved buffers and re-checks the caller's x).  Only
-  // the norm-1-backward operand of gbF must be present to be eligible; the launch always
-  // supplies all of it, so the query below gets a stand-in for every pointer it tests.
+  // table for both of its uses (the launch passes st2 twice).  Only the norm-1-backward
+  // operand of gbF must be present to be eligible; the launch always supplies all of it, so
+  // the query below gets a stand-in for every pointer it tests.
   pl.dualA = gemm_dual_eligible(dt, pl.duA);
   // The norm-1/PReLU-1 backward runs inside the first 1x1's two gradient GEMMs (bf16,
   // weight-stationary data-gradient kernel); else norm1_bwd_kernel.
@@ -208,8 +206,8 @@ TbPlan tb_plan(const ctn_tblock_desc* d, bool backward) {
   }
   pl.foldX = pl.fused1 && pl.fold && (ws_fold_mask() & 2);
   pl.partsD = dw_parts_per_group(pl.dwB);
-  pl.chunks2 = pl.dualA ? gemm_dual_ranges(pl.duA) : gemm_cols_default_chunks(pl.c2);
-  pl.chunks1 = gemm_cols_chunks(dt, pl.c1);
+  pl.chunks2 = pl.dualA ? gemm_dual_ranges(pl.duA) : gemm_cols_chunks(pl.c2);
+  pl.chunks1 = gemm_cols_chunks(pl.c1);
   pl.dwb = dw_blocks(pl.dwB);
   pl.dws = dw_col_stride(pl.dwB);
   pl.ewb = ew_blocks(pl.dwB);
@@ -361,9 +359,9 @@ BnLayout bn_layout(const ctn_tblock_desc* d, int backward, void* ws) {
     L.slabD = c.take<double2>((size_t)M * dw_parts_per_group(da) * sizeof(double2));
     L.colD = c.take<float>((size_t)dw_blocks(da) * dw_col_stride(da) * sizeof(float));
     L.alphaSlab = c.take<float>((size_t)nb * sizeof(float));
-    L.chunks2 = gemm_cols_default_chunks(tb_cols2(d, NORM_GLN));
+    L.chunks2 = gemm_cols_chunks(tb_cols2(d, NORM_GLN));
     L.cpart2 = c.take<float>((size_t)L.chunks2 * B * H * sizeof(float));
-    L.chunks1 = gemm_cols_default_chunks(tb_cols1(d));
+    L.chunks1 = gemm_cols_chunks(tb_cols1(d));
     L.cpart1 = c.take<float>((size_t)L.chunks1 * B * H * sizeof(float));
     const long HB = (long)H * B, dwb = dw_blocks(da);
     const size_t ntmp = sr_tmp(L.chunks2, HB) + sr_tmp(L.chunks1, HB) + 2 * sr_tmp(dwb, H) +
@@ -776,7 +774,7 @@ extern "C" int ctn_tblock_plan(const ctn_tblock_desc* d, int backward, char* out
     s = std::string("pairA=") + (pl.dualA ? "dual_ws" : pl.rows_kernel(pl.ga)) + (pl.dualA ? "" : "+cols") +
         ",dw_bwd=" + pl.dw_kernel(true);
     if (pl.fused1)
-      s += std::string(",gx=ws_n1bwd,dW1=") + pl.cols_kernel(pl.c1);
+      s += ",gx=ws_n1bwd,dW1=cols";
     else
       s += ",n1bwd=ew,gx+dW1=rows+cols";
   }

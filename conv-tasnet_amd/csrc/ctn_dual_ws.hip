@@ -100,8 +100,6 @@ static_assert(DV_PF >= 1 && DV_PF <= DV_NSL - 1, "ring look-ahead");
 // blocks per wave means fewer waves share and transform each B fragment, at the price of
 // more A fragment reads per wave: CJ=1 79.5 us, CJ=2 85.0 (bench shape).
 constexpr int DV_CJ = 1;
-// COLS mode (no operand transform to share): the split that reads the fewest fragments
-constexpr int DV_CJC = 4;
 
 // Static wave priority per role (s_setprio once at the role's start).  The SIMD's issue
 // arbiter serves the higher priority first, so the memory wave sharing a SIMD with three
@@ -222,14 +220,10 @@ CTN_DEV void dv_signal(uint32_t* f, uint32_t gen) {
   asm volatile("" ::: "memory");
 }
 
-// COLS: the column GEMM alone (ctn_gemm.hip's GemmCols dW = A^T B with plain operands,
-// e.g. dW1 = gh1^T . x): no row waves, op = identity, and the partial stored transposed
-// (Dpart[range][n][k], the GemmCols layout [chunk][P][Q] with P = Nout, Q = Kred) through
-// LDS at the end.  12 waves: column waves 0-7, memory waves 8-11.
-template <int NK, int NSL, int PF, bool COLS = false>
-__global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dual_ws_kernel(GemmDual p) {
-  constexpr int NR = COLS ? 0 : DV_NR;      // row waves
-  constexpr int ND = NR + DV_NC;            // waves that publish DONE
+// 16 waves: row waves 0-3, column waves 4-11, memory waves 12-15
+template <int NK, int NSL, int PF>
+__global__ __launch_bounds__(DV_NT) void gemm_dual_ws_kernel(GemmDual p) {
+  constexpr int NR = DV_NR, ND = DV_ND;
   constexpr int TM = DV_TM, KB = DV_KB, KR = DV_KR, NS = DV_NS;
   constexpr int SLOT = DV_SLOT;
   static_assert(NSL * SLOT <= 160 * 1024 - 2048, "LDS budget");
@@ -240,7 +234,7 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
   // cLN: the four row waves' per-row partials of a tile, combined in LDS before storing
   // (S entries per row instead of 4 S), two tiles deep, and one generation
   // word per (buffer, row wave)
-  constexpr bool CLNC = NK == NORM_CLN && !COLS;
+  constexpr bool CLNC = NK == NORM_CLN;
   __shared__ __attribute__((aligned(16))) double2 cln_scr[CLNC ? 2 : 1][CLNC ? DV_NR * DV_TM : 1];
   __shared__ __attribute__((aligned(16))) uint32_t fl_rows[2][4];
 
@@ -271,24 +265,11 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
   if (tid < NSL * 4) (&fl_full[0][0])[tid] = 0u;
   else if (tid < NSL * (4 + ND)) (&fl_done[0][0])[tid - NSL * 4] = 0u;
   else if (tid < NSL * (4 + ND) + 8) (&fl_rows[0][0])[tid - NSL * (4 + ND)] = 0u;
-  if constexpr (!COLS)
-    if (tid < 2 * NS) sgb[tid / NS][tid % NS] = (tid < NS ? p.bop.gamma : p.bop.beta)[n0 + tid % NS];
+  if (tid < 2 * NS) sgb[tid / NS][tid % NS] = (tid < NS ? p.bop.gamma : p.bop.beta)[n0 + tid % NS];
   __syncthreads();
 
-  const float eal = COLS ? 0.f : p.alpha[0];
+  const float eal = p.alpha[0];
   const int kmax = ws_runs_kmax(ntile, nr, tpu);
-  // COLS: the workgroup's transposed partial [n - n0][k] from the LDS image (COLS_LDT
-  // floats per row) as whole 1-KiB rows of Dpart[range][n][k], by every wave
-  constexpr int COLS_LDT = KR + 4;
-  static_assert(!COLS || NS * COLS_LDT * 4 <= NSL * DV_SLOT, "transpose image fits the ring");
-  auto store_tr = [&](float* Dp) __attribute__((always_inline)) {
-    const float* img = reinterpret_cast<const float*>(smem);
-    for (int idx = tid; idx < NS * (KR / 4); idx += (DV_NC + DV_NMW) * 64) {
-      const int nl = idx / (KR / 4), k4 = idx % (KR / 4);
-      *reinterpret_cast<float4*>(Dp + (size_t)(n0 + nl) * KR + 4 * k4) =
-          *reinterpret_cast<const float4*>(img + nl * COLS_LDT + 4 * k4);
-    }
-  };
   if (wid < NR) {
     // ======================= row waves =======================
     dv_prio<DV_PRIO_ROW, NK>();
@@ -465,7 +446,7 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
     // dW2 += gy_tile^T . op(d)_tile, the reduction over the tile's 32 frame rows
     // the slice's 16 x 8 blocks of 16 x 16: waves in a (NC / (8 / CJ)) x (8 / CJ) grid,
     // each CI x CJ blocks
-    constexpr int CJ = COLS ? DV_CJC : DV_CJ, CI = 16 * (8 / CJ) / DV_NC;
+    constexpr int CJ = DV_CJ, CI = 16 * (8 / CJ) / DV_NC;
     static_assert(CI >= 2 && CI <= 16 && CI % 2 == 0, "column split");
     const int c = wid - NR, wp = c / (8 / CJ), wn = c % (8 / CJ);
     DV_STAMP_DECL;
@@ -493,10 +474,10 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
     float cg[CJ], cb[CJ];
 #pragma unroll
     for (int j = 0; j < CJ; ++j) {
-      cg[j] = COLS ? 0.f : sgb[0][16 * (CJ * wn + j) + lr];
-      cb[j] = COLS ? 0.f : sgb[1][16 * (CJ * wn + j) + lr];
+      cg[j] = sgb[0][16 * (CJ * wn + j) + lr];
+      cb[j] = sgb[1][16 * (CJ * wn + j) + lr];
     }
-    const float bal = COLS ? 0.f : p.bop.alpha[0];
+    const float bal = p.bop.alpha[0];
     // one tile's B fragments (raw d -> op(d)), read from the ring slot at `base`
     auto load_b = [&](auto le1, int t, const char* base, bf16x8_t* bfr) __attribute__((always_inline)) {
       constexpr bool LE1 = decltype(le1)::value;
@@ -507,38 +488,36 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
         const s16x4_t hi = dv_tr(bb + (bbase[1] ^ (j << 5)));
         bfr[j] = bf16x8_t{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
       }
-      if constexpr (!COLS) {
-        float mu[8], rs[8];
-        if constexpr (NK == NORM_GLN) {
-          const float2 st = *reinterpret_cast<const float2*>(base + OFF_ST);
+      float mu[8], rs[8];
+      if constexpr (NK == NORM_GLN) {
+        const float2 st = *reinterpret_cast<const float2*>(base + OFF_ST);
 #pragma unroll
-          for (int e = 0; e < 8; ++e) mu[e] = st.x, rs[e] = st.y;
-        } else {
+        for (int e = 0; e < 8; ++e) mu[e] = st.x, rs[e] = st.y;
+      } else {
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float4 st = *reinterpret_cast<const float4*>(base + OFF_ST + 64 * lg + 16 * k);
-            mu[2 * k] = st.x, rs[2 * k] = st.y, mu[2 * k + 1] = st.z, rs[2 * k + 1] = st.w;
-          }
+        for (int k = 0; k < 4; ++k) {
+          const float4 st = *reinterpret_cast<const float4*>(base + OFF_ST + 64 * lg + 16 * k);
+          mu[2 * k] = st.x, rs[2 * k] = st.y, mu[2 * k + 1] = st.z, rs[2 * k + 1] = st.w;
         }
-        const int tk = (t * TM) % Kp;
+      }
+      const int tk = (t * TM) % Kp;
 #pragma unroll
-        for (int j = 0; j < CJ; ++j) {
-          v4u v = __builtin_bit_cast(v4u, bfr[j]);
+      for (int j = 0; j < CJ; ++j) {
+        v4u v = __builtin_bit_cast(v4u, bfr[j]);
 #pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            float x0 = __uint_as_float(v[k] << 16), x1 = __uint_as_float(v[k] & 0xffff0000u);
-            x0 = dv_prelu<LE1>(x0, bal);
-            x1 = dv_prelu<LE1>(x1, bal);
-            x0 = fmaf(x0 - mu[2 * k], rs[2 * k] * cg[j], cb[j]);
-            x1 = fmaf(x1 - mu[2 * k + 1], rs[2 * k + 1] * cg[j], cb[j]);
-            if constexpr (NK == NORM_CLN) {   // padded frames: statistics not finite
-              if (tk + 8 * lg + 2 * k >= Kv) x0 = 0.f;
-              if (tk + 8 * lg + 2 * k + 1 >= Kv) x1 = 0.f;
-            }
-            v[k] = pk_bf16(x0, x1);
+        for (int k = 0; k < 4; ++k) {
+          float x0 = __uint_as_float(v[k] << 16), x1 = __uint_as_float(v[k] & 0xffff0000u);
+          x0 = dv_prelu<LE1>(x0, bal);
+          x1 = dv_prelu<LE1>(x1, bal);
+          x0 = fmaf(x0 - mu[2 * k], rs[2 * k] * cg[j], cb[j]);
+          x1 = fmaf(x1 - mu[2 * k + 1], rs[2 * k + 1] * cg[j], cb[j]);
+          if constexpr (NK == NORM_CLN) {   // padded frames: statistics not finite
+            if (tk + 8 * lg + 2 * k >= Kv) x0 = 0.f;
+            if (tk + 8 * lg + 2 * k + 1 >= Kv) x1 = 0.f;
           }
-          bfr[j] = __builtin_bit_cast(bf16x8_t, v);
+          v[k] = pk_bf16(x0, x1);
         }
+        bfr[j] = __builtin_bit_cast(bf16x8_t, v);
       }
     };
     auto a_frag = [&](const char* base, int i) __attribute__((always_inline)) {
@@ -573,28 +552,11 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
       }
       DV_ACC(3, tl0);
     };
-    if (COLS || bal <= 1.f) run(std::true_type{});
+    if (bal <= 1.f) run(std::true_type{});
     else run(std::false_type{});
     DV_STAMP_STORE;
     // dW2 partial of this workgroup: lane holds D[(wp*CI+i)*16 + 4lg + e][n0 + (wn*CJ+j)*16 + lr]
     float* Dp = p.Dpart + (size_t)rr * KR * p.Nout;
-    if constexpr (COLS) {
-      // transposed through LDS (the ring is idle once every wave is past the barrier):
-      // image [n - n0][k] fp32, rows padded by 4 floats against bank conflicts
-      float* img = reinterpret_cast<float*>(smem);
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < CI; ++i)
-#pragma unroll
-        for (int j = 0; j < CJ; ++j) {
-          const int nl = (wn * CJ + j) * 16 + lr;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) img[nl * COLS_LDT + (wp * CI + i) * 16 + 4 * lg + e] = dacc[i][j][e];
-        }
-      __syncthreads();
-      store_tr(Dp);
-      return;
-    }
 #pragma unroll
     for (int i = 0; i < CI; ++i)
 #pragma unroll
@@ -647,8 +609,8 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
   // utterance pair, lanes 0..1).  Other lanes read out of range (zeros).
   const bool st_lane = NK == NORM_CLN || lane < 2;
   const uint32_t soff = st_lane ? (uint32_t)(lane * 4) : DU_OOB;
-  const bool st_wave = !COLS && mw == 0;
-  const float bal = COLS ? 0.f : p.bop.alpha[0];
+  const bool st_wave = mw == 0;
+  const float bal = p.bop.alpha[0];
   // DMA instructions per wave and tile: 7 (st_wave), else 6 (waves 1..3)
 
   auto dma = [&](int t) __attribute__((always_inline)) {
@@ -700,15 +662,10 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
   // (the loop no longer depends on alpha; the two copies are what the shipped kernel holds,
   // and folding them changes its code and register counts: not part of a pure deletion)
   if (t0 < t1) {
-    if (COLS || bal <= 1.f) run(std::true_type{});
+    if (bal <= 1.f) run(std::true_type{});
     else run(std::false_type{});
   }
   DV_STAMP_STORE;
-  if constexpr (COLS) {   // the column waves' two barriers, then a share of the stores
-    __syncthreads();
-    __syncthreads();
-    store_tr(p.Dpart + (size_t)rr * KR * p.Nout);
-  }
 }
 
 }  // namespace
@@ -716,14 +673,6 @@ __global__ __launch_bounds__(COLS ? (DV_NC + DV_NMW) * 64 : DV_NT) void gemm_dua
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// Row ranges of a launch over `rows` frame rows with `nout` sliced channels: the grid is
-// ranges * (nout / 128) workgroups
-static int dv_ranges(long rows, int nout) {
-  const long nt = rows / DV_TM;
-  const int want = DV_GRID / (nout / DV_NS);
-  return (int)(nt < want ? nt : want);
-}
-
 // CTN_GEMM_DUAL bit 0 (default 1): pair A runs as this one kernel; cleared, as the row GEMM
 // + column GEMM kernels (109 us against 62 + 60 us at the time of the choice).
 // Every other bit is ignored.  Read on every query so a process can compare both paths
@@ -746,7 +695,12 @@ bool gemm_dual_eligible(DType dt, const GemmDual& p) {
   return true;
 }
 
-int gemm_dual_ranges(const GemmDual& p) { return dv_ranges(p.g.rows(), p.Nout); }
+// Row ranges of a launch: the grid is ranges * (Nout / 128) workgroups
+int gemm_dual_ranges(const GemmDual& p) {
+  const long nt = p.g.rows() / DV_TM;
+  const int want = DV_GRID / (p.Nout / DV_NS);
+  return (int)(nt < want ? nt : want);
+}
 
 // gLN: the run layout of the statistics partials (one run list per range, slice and row wave)
 static WsRuns gemm_dual_runs(const GemmDual& p) {
@@ -787,41 +741,6 @@ hipError_t launch_gemm_dual(const GemmDual& pa, hipStream_t s) {
     hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_GLN, DV_NSL, DV_PF>), grid, dim3(DV_NT), 0, s, p);
   else
     hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_CLN, DV_NSL, DV_PF>), grid, dim3(DV_NT), 0, s, p);
-  return hipGetLastError();
-}
-
-// The column GEMM alone (GemmCols, plain bf16 operands): dW[P][Q] partials per row range
-// = A^T B with A [rows][P] (P = Nout, sliced by 128 per workgroup) and B [rows][Q]
-// (Q = Kred = 256, whole rows), i.e. the dual's column part with the roles of its
-// operands swapped: its "A" tile is B and its raw-B slice is A.
-// Off by default (CTN_COLS_WS=1 to enable): 47.8 us against the tiled kernel's 49.4 in the
-// step, but twice the partial bytes (64 row ranges instead of 32 chunks) cost the slab
-// reduction more than that: bench 2129 vs 2142 utt/s.
-bool gemm_cols_ws_eligible(DType dt, const GemmCols& c) {
-  const char* e = getenv("CTN_COLS_WS");
-  if (!e || atoi(e) == 0) return false;
-  if (dt != BF16 || c.aop.kind != OP_PLAIN || c.bop.kind != OP_PLAIN) return false;
-  if (c.Q != DV_KR || c.P % DV_NS || DV_GRID % (c.P / DV_NS)) return false;
-  if (c.g.Kp % DV_TM || c.lda % 8 || c.ldb % 8 || c.g.rows() / DV_TM < 1) return false;
-  if (c.g.rows() * (c.P > c.Q ? c.P : c.Q) * 2 >= (1L << 31)) return false;   // 32-bit offsets
-  if (((uintptr_t)c.A | (uintptr_t)c.B | (uintptr_t)c.Cpart) & 15) return false;
-  return true;
-}
-
-int gemm_cols_ws_ranges(const GemmCols& c) { return dv_ranges(c.g.rows(), c.P); }
-
-hipError_t launch_gemm_cols_ws(const GemmCols& c, hipStream_t s) {
-  GemmDual p{};
-  p.err = device_error_word();
-  p.g = c.g;
-  p.Kred = c.Q;
-  p.Nout = c.P;
-  p.A = c.B; p.lda = c.ldb;     // whole 256-channel rows: the fragment-order tile
-  p.Bm = c.A; p.ldb = c.lda;    // the 128-channel slice: raw B
-  p.Dpart = c.Cpart;            // [range][P][Q]
-  const dim3 grid(gemm_cols_ws_ranges(c) * (c.P / DV_NS));
-  hipLaunchKernelGGL((gemm_dual_ws_kernel<NORM_GLN, DV_NSL, DV_PF, true>), grid, dim3((DV_NC + DV_NMW) * 64), 0,
-                     s, p);
   return hipGetLastError();
 }
 

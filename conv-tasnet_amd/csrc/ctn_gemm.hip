@@ -12,7 +12,6 @@
 //
 // MFMA: bf16 storage -> v_mfma_f32_16x16x32_bf16; fp32 storage (parity mode)
 // -> v_mfma_f32_16x16x4_f32 (exact fp32 products, fp32 accumulate).
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -337,20 +336,13 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(GemmRows p) {
 }
 
 // rows per tile: 64 (more workgroups per CU to hide load latency on the short
-// k loops of this model) unless CTN_GEMM_BM=128 is set (A/B experiments)
-static int rows_bm() {
-  static int bm = 0;
-  if (!bm) {
-    const char* e = getenv("CTN_GEMM_BM");
-    bm = (e && atoi(e) == 128) ? 128 : 64;
-  }
-  return bm;
-}
+// k loops of this model)
+constexpr int ROWS_BM = 64;
 
 int gemm_rows_tiles_per_group(DType dt, const GemmRows& p) {
   if (gemm_ws_eligible(dt, p)) return gemm_ws_group_parts(p);
   const int ncol = (p.Nout + RBN - 1) / RBN;
-  return p.norm == NORM_GLN ? (p.g.Kp / rows_bm()) * ncol : ncol;
+  return p.norm == NORM_GLN ? (p.g.Kp / ROWS_BM) * ncol : ncol;
 }
 
 StatFold gemm_rows_stat_fold(DType dt, const GemmRows& p, const double2* slab, double cnt, float eps, int mode,
@@ -369,10 +361,8 @@ StatFold gemm_rows_stat_fold(DType dt, const GemmRows& p, const double2* slab, d
 template <typename T, int OPK, int NK, int EPI>
 static hipError_t launch_rows_t(const GemmRows& p, hipStream_t s) {
   const int ncol = (p.Nout + RBN - 1) / RBN;
-  const int bm = rows_bm();
-  const int nrow = (int)(p.g.rows() / bm);
-  if (bm == 128) hipLaunchKernelGGL((gemm_rows_kernel<T, OPK, NK, EPI, 128>), dim3(nrow * ncol), dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((gemm_rows_kernel<T, OPK, NK, EPI, 64>), dim3(nrow * ncol), dim3(256), 0, s, p);
+  const int nrow = (int)(p.g.rows() / ROWS_BM);
+  hipLaunchKernelGGL((gemm_rows_kernel<T, OPK, NK, EPI, ROWS_BM>), dim3(nrow * ncol), dim3(256), 0, s, p);
   return hipGetLastError();
 }
 
@@ -709,21 +699,15 @@ __global__ __launch_bounds__(256 * CKS) void gemm_cols_kernel(GemmCols p) {
     }
 }
 
-// target workgroup count of a column GEMM (CTN_COLS_WG overrides it for A/B experiments)
-static int cols_wg_target() {
-  static int t = 0;
-  if (!t) {
-    const char* e = getenv("CTN_COLS_WG");
-    const int v = e ? atoi(e) : 0;
-    t = v >= 64 && v <= 4096 ? v : 256;
-  }
-  return t;
-}
+// target workgroup count of a column GEMM: one 8-wave workgroup per CU; 128 and 512
+// measured slower
+constexpr int COLS_WG_TARGET = 256;
 
-int gemm_cols_default_chunks(const GemmCols& p) {
+// Partial count of a column GEMM (the nchunks launch_gemm_cols is given)
+int gemm_cols_chunks(const GemmCols& p) {
   const int tiles = ((p.P + CBP - 1) / CBP) * ((p.Q + CBQ - 1) / CBQ);
   const long rows = p.g.rows();
-  int ch = (cols_wg_target() + tiles - 1) / tiles;   // ~256 workgroups of CKS x 4 waves
+  int ch = (COLS_WG_TARGET + tiles - 1) / tiles;   // ~256 workgroups of CKS x 4 waves
   const long maxch = (rows + CKS * CKR * 4 - 1) / (CKS * CKR * 4);   // >= 4 k-steps per group
   if (ch > maxch) ch = (int)maxch;
   return ch < 1 ? 1 : ch;
@@ -745,14 +729,7 @@ static hipError_t dispatch_cols_nk(const GemmCols& p, hipStream_t s) {
   return hipErrorInvalidValue;
 }
 
-// Partial count of a column GEMM as launch_gemm_cols will run it: the wave-specialised
-// kernel's row ranges where it applies (ctn_dual_ws.hip), else the tiled kernel's chunks.
-int gemm_cols_chunks(DType dt, const GemmCols& p) {
-  return gemm_cols_ws_eligible(dt, p) ? gemm_cols_ws_ranges(p) : gemm_cols_default_chunks(p);
-}
-
 hipError_t launch_gemm_cols(DType dt, const GemmCols& p, hipStream_t s) {
-  if (gemm_cols_ws_eligible(dt, p) && p.nchunks == gemm_cols_ws_ranges(p)) return launch_gemm_cols_ws(p, s);
   if (p.g.Kp % CKR != 0 || p.P % 8 != 0 || p.Q % 8 != 0 || p.nchunks < 1 || p.g.rows() >= (1L << 31))
     return hipErrorInvalidValue;
   const int nk = p.bop.kind != OP_PLAIN ? p.bop.norm : 0;

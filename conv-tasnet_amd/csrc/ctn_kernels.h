@@ -95,7 +95,7 @@ struct GemmCols {
   float* Cpart;                // [nchunks][P][Q]
   int nchunks;
 };
-int gemm_cols_default_chunks(const GemmCols& p);
+int gemm_cols_chunks(const GemmCols& p);   // partial count (nchunks) of a launch
 hipError_t launch_gemm_cols(DType dt, const GemmCols& p, hipStream_t s);
 
 // ---- dual GEMM (ctn_dual_ws.hip): a row GEMM and the weight gradient that shares
@@ -116,7 +116,7 @@ struct GemmDual {
   int norm = 0;
   double2* grp_slab = nullptr;
   const void* Bm; int ldb;
-  RowOp bop;                   // OP_PLAIN or OP_PRELU_NORM with final statistics
+  RowOp bop;                   // OP_PRELU_NORM with final statistics
   float* Dpart;                // [gemm_dual_ranges][Kred][Nout]
   uint32_t* err = nullptr;     // device error word (generation-word timeouts), set by the launcher
 };
@@ -126,12 +126,6 @@ int gemm_dual_group_parts(const GemmDual& p);
 StatFold gemm_dual_stat_fold(const GemmDual& p, const double2* slab, double cnt, float eps, int mode,
                              float2* out);
 hipError_t launch_gemm_dual(const GemmDual& p, hipStream_t s);
-// the same kernel's column part alone for plain bf16 column GEMMs (dW1 = gh1^T . x):
-// chosen by launch_gemm_cols when nchunks == gemm_cols_ws_ranges (gemm_cols_chunks)
-bool gemm_cols_ws_eligible(DType dt, const GemmCols& c);
-int gemm_cols_ws_ranges(const GemmCols& c);
-hipError_t launch_gemm_cols_ws(const GemmCols& c, hipStream_t s);
-int gemm_cols_chunks(DType dt, const GemmCols& c);   // partial count the launch will use
 
 // ---- statistics ------------------------------------------------------------
 // slab: [G][nparts] double2 partials -> out[G] float2

@@ -260,6 +260,13 @@ _TB_RECORDED_ENV = {
     ("CTN_DUAL_WS", "0"): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
     ("CTN_DW_WAVE", "0"): (672000, 275550324, 65261172, 210289408, "gemm1=ws,dw_fwd=lane,gemm2=ws",
                            "pairA=dual_ws,dw_bwd=lane,gx=ws_n1bwd,dW1=cols"),
+    # no longer read (the dual kernel's column-only mode, the 128-row tiled row GEMM and the
+    # column GEMM's workgroup-target override are retired): the default plan.
+    # (Before, CTN_COLS_WS=1 and CTN_COLS_WG=512 each gave 292327540 / 82038388 here;
+    # CTN_GEMM_BM=128 moved only the shapes that run the tiled row GEMM, not this one.)
+    ("CTN_COLS_WS", "1"): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
+    ("CTN_GEMM_BM", "128"): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
+    ("CTN_COLS_WG", "512"): (672000, 275550324, 65261172, 210289408, _F_FAST, _B_FAST),
 }
 
 
@@ -287,7 +294,6 @@ def test_tblock_sizes_and_plans_match_recorded(lib, monkeypatch):
     for var, _ in _TB_RECORDED_ENV:
         monkeypatch.delenv(var, raising=False)
     monkeypatch.delenv("CTN_WS_FOLD", raising=False)
-    monkeypatch.delenv("CTN_COLS_WS", raising=False)
     for (norm, dtype, i), want in _TB_RECORDED.items():
         for causal in (0, 1):
             got = _tb_sizes_and_plans(lib, norm, causal, dtype, _TB_SHAPES[i])

@@ -20,7 +20,7 @@ library's contract: padded rows are zero).
   (b) test_gauss_elementwise  N(0,1) x and gy, N(0, 0.05^2) w, rounded to bf16; per element
                            |y - ref| <= 2^-8 |ref| + Kred 2^-23 S,  S = |x| . |w|^T in fp64
                            (fp32 storage: the second term alone); gx likewise with
-                           Kred = cout; gw by the project's bound (test_gpu_cols_ws.py):
+                           Kred = cout; gw by the project's bound (test_gpu_cols_gemm.py):
                            relative L2 < 1e-5 against the fp32 matmul of the same operands.
   (c) test_guard_bands     y and gx as views into larger buffers between 64 sentinel rows:
                            the clamped look-ahead tiles past a range's end are "never

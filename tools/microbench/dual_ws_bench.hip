@@ -2,7 +2,7 @@
 //   * run-to-run reproducibility (every byte of C and of the dW2 partials, and the norm-2
 //     statistics per group summed from the partials);
 //   * time per launch (hipEvents over NIT launches);
-//   * the per-role wait stamps (-DCTN_DV_STAMP=1) and the kernel's COLS mode.
+//   * the per-role wait stamps (-DCTN_DV_STAMP=1).
 // Build with -DCTN_DV_EXP=<bits> for the bound-finding variants (timing only).
 // Usage: dual_ws_bench [M] [K] [g|c] [runs].  Not part of the library.
 #include <stdio.h>
@@ -163,26 +163,5 @@ int main(int argc, char** argv) {
     }
   }
 #endif
-  // the same kernel's COLS mode (dW1 = gh1^T . x shape: A = d [rows][H], B = gy [rows][B])
-  {
-    GemmCols c{};
-    c.g = g.g; c.P = H; c.Q = B;
-    c.A = d; c.lda = H; c.B = gy; c.ldb = B;
-    c.nchunks = gemm_cols_ws_ranges(c);
-    float* cp; CK(hipMalloc(&cp, (size_t)c.nchunks * H * B * 4));
-    c.Cpart = cp;
-    if (gemm_cols_ws_eligible(BF16, c)) {
-      for (int i = 0; i < 3; ++i) CK(launch_gemm_cols_ws(c, 0));
-      CK(hipDeviceSynchronize());
-      CK(hipEventRecord(e0, 0));
-      for (int i = 0; i < NIT; ++i) CK(launch_gemm_cols_ws(c, 0));
-      CK(hipEventRecord(e1, 0));
-      CK(hipEventSynchronize(e1));
-      float ms; CK(hipEventElapsedTime(&ms, e0, e1));
-      const double us = ms * 1e3 / NIT, cb = rows * (B + H) * 2.0;
-      printf("COLS CJC=%d M=%d K=%d %8.1f us  %7.0f GB/s (alg. bytes, %d ranges)\n", DV_CJC, M, K, us, cb / us * 1e-3,
-             c.nchunks);
-    }
-  }
   return 0;
 }
