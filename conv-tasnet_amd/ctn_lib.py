@@ -73,6 +73,11 @@ class BssDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("M", "C", "E", "T", "flen")]
 
 
+class StoiDesc(ctypes.Structure):
+    """ctn_stoi_desc (include/ctn.h): STOI / ESTOI; T is the row stride in samples."""
+    _fields_ = [(n, c_int32) for n in ("M", "C", "E", "T", "up", "down", "Hl")]
+
+
 class DmixDesc(ctypes.Structure):
     """ctn_dmix_desc (include/ctn.h): dynamic mixing on the device."""
     _fields_ = ([(n, c_int32) for n in ("M", "C", "T", "n_utts", "n_elig", "pool_dtype", "level_mode", "max_tries")] +
@@ -176,6 +181,9 @@ _SIGS = {
     "ctn_pit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p]),
     "ctn_bss_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_bss_eval": (ctypes.c_int, [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_stoi_table_doubles": (c_size_t, [c_void_p]),
+    "ctn_stoi_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_stoi_eval": (ctypes.c_int, [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "ctn_dmix_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_dmix_draw": (ctypes.c_int, [c_void_p] * 4 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "ctn_dmix_mix": (ctypes.c_int, [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),

@@ -23,7 +23,10 @@ Same flags and printout as the reference.  Differences, each deliberate:
   DESIGN.md §18) instead of once per utterance on the host; same printout;
 * ``--chunk_s SEC`` (default 0: nothing changes) separates every utterance in overlapping
   windows of SEC seconds stitched on the device (``longform.ChunkedSeparator``, DESIGN.md
-  §23), so that the cost of windowing in SI-SNRi can be measured on a manifest.
+  §23), so that the cost of windowing in SI-SNRi can be measured on a manifest;
+* ``--cal_stoi 1`` (default 0: nothing changes) also scores STOI and ESTOI of a whole minibatch
+  on the device (``cal_STOI_batch``, stoi.py, csrc/ctn_stoi.hip), for the
+  paired estimates and for the unprocessed mixture; the reference has no such option.
 """
 import argparse
 
@@ -58,6 +61,8 @@ parser.add_argument('--chunk_s', default=0.0, type=float,
                     help='Window in seconds for windowed separation (0: whole signal)')
 parser.add_argument('--chunk_overlap_s', default=None, type=float,
                     help='Overlap of neighbouring windows in seconds (default: half of --chunk_s)')
+parser.add_argument('--cal_stoi', default=0, type=int,
+                    help='1: also compute STOI and ESTOI on the device (estimates and mixture, batched HIP kernels)')
 
 
 def reorder_inverse(est, source, lengths):
@@ -74,16 +79,24 @@ class Evaluator:
     the same per-utterance printout and averages).  Minibatches are separated on the
     device, scored there in fp64 (SI-SNRi, cal_SISNRi_batch) and, with --cal_sdr, on the
     host (SDRi, cal_SDRi) or with --sdr_device on the device (cal_SDRi_batch); ``records``
-    keeps one (SI-SNRi, SDRi or None) per utterance."""
+    keeps one (SI-SNRi, SDRi or None) per utterance; with --cal_stoi, ``stoi_records`` keeps one
+    (STOI, ESTOI, mixture STOI, mixture ESTOI) per utterance (cal_STOI_batch)."""
 
     def __init__(self, args):
         self.args = args
+        if getattr(args, 'cal_stoi', 0):
+            import stoi
+            try:
+                stoi.device_ratio(args.sample_rate)
+            except ValueError as e:
+                raise SystemExit(f"--cal_stoi 1: {e}")
         self.model = ConvTasNet.load_model(args.model_path)
         print(self.model)
         self.model.eval().cuda()
         dataset = AudioDataset(args.data_dir, args.batch_size, sample_rate=args.sample_rate, segment=-1)
         self.loader = AudioDataLoader(dataset, batch_size=1, num_workers=args.num_workers)
         self.records = []
+        self.stoi_records = []
         from separate import make_chunker
         self.chunker = make_chunker(self.model, getattr(args, 'chunk_s', 0.0), getattr(args, 'chunk_overlap_s', None),
                                     args.sample_rate)
@@ -122,17 +135,29 @@ class Evaluator:
     def run(self):
         for mixture, lengths, source in self.loader:
             mixture, lengths, source = mixture.cuda(), lengths.cuda(), source.cuda()
-            for si, sd in self._score(mixture, lengths, source, self._separate(mixture, lengths, source)):
+            paired = self._separate(mixture, lengths, source)
+            st = [None] * mixture.size(0)
+            if getattr(self.args, 'cal_stoi', 0):
+                st = list(zip(*(v.tolist() for v in cal_STOI_batch(source, paired, mixture, lengths,
+                                                                    self.args.sample_rate))))
+            for (si, sd), sv in zip(self._score(mixture, lengths, source, paired), st):
                 self.records.append((si, sd))
                 print("Utt", len(self.records))
                 if sd is not None:
                     print("\tSDRi={0:.2f}".format(sd))
                 print("\tSI-SNRi={0:.2f}".format(si))
+                if sv is not None:
+                    self.stoi_records.append(sv)
+                    print("\tSTOI={0:.3f}".format(sv[0]))
+                    print("\tESTOI={0:.3f}".format(sv[1]))
         n = len(self.records)
         if self.args.cal_sdr:
             print("Average SDR improvement: {0:.2f}".format(sum(r[1] for r in self.records) / n))
         mean_sisnri = sum(r[0] for r in self.records) / n
         print("Average SISNR improvement: {0:.2f}".format(mean_sisnri))
+        if self.stoi_records:
+            for k, name in enumerate(("STOI", "ESTOI", "STOI of the mixture", "ESTOI of the mixture")):
+                print("Average {0}: {1:.3f}".format(name, sum(r[k] for r in self.stoi_records) / n))
         return mean_sisnri
 
 
@@ -174,6 +199,23 @@ def cal_SDRi_batch(source, estimate, mixture, lengths, flen=None):
         else:
             out[b] = np.mean(bss_eval._assign(sdr[b, :C], sir[b, :C], sar[b, :C], True)[0] - sdr[b, C])
     return out
+
+
+def cal_STOI_batch(source, estimate, mixture, lengths, fs=8000):
+    """STOI and ESTOI of every utterance of a padded batch with stoi.py's device path: source /
+    estimate [B, C, T] (estimate c paired with source c), mixture [B, T], lengths [B] ->
+    four numpy [B]: STOI and ESTOI of the estimates, STOI and ESTOI of the mixture against
+    each source, each the mean over the sources.  One library call scores E = C + 1 signals
+    per utterance, the C estimates and the mixture."""
+    import stoi
+    if source.dim() != 3 or source.shape != estimate.shape:
+        raise ValueError(f"shape mismatch: sources {tuple(source.shape)}, estimates {tuple(estimate.shape)}")
+    B, C, T = source.shape
+    sigs = torch.cat((estimate, mixture.reshape(B, 1, T).to(estimate.dtype)), dim=1)
+    d, de, _, _ = stoi.stoi_device(source, sigs, lengths, fs)                 # [B, C + 1, C]
+    own = torch.arange(C, device=d.device)
+    out = (d[:, own, own].mean(1), de[:, own, own].mean(1), d[:, C, :].mean(1), de[:, C, :].mean(1))
+    return tuple(v.cpu().numpy() for v in out)
 
 
 def cal_SISNRi(src_ref, src_est, mix):

@@ -246,6 +246,63 @@ int ctn_bss_eval(const ctn_bss_desc* d, const float* refs /*[M][C][T]*/, const f
                  void* ws, size_t ws_bytes, void* stream);
 
 /* -------------------------------------------------------------------------
+ * STOI and ESTOI (short-time objective intelligibility: Taal et al., IEEE TASLP 19(7), 2011;
+ * Jensen & Taal, IEEE TASLP 24(11), 2016) as pystoi 0.3+ computes them, for M utterances,
+ * C references and E scored signals per utterance: score[m][e][j] = { STOI, ESTOI } of
+ * signal e against reference j.  Added within ABI v13 without a version bump (nothing
+ * existing changed): callers probe for the symbol.  fp32 inputs with row stride T samples;
+ * utterance m uses its first lengths[m] samples and never reads the rest (it may hold NaN).
+ *
+ * `tab` (device memory, ctn_stoi_table_doubles(d) doubles, computed by the caller in fp64;
+ * the kernels evaluate no trigonometric function):
+ *   [0, 256)    the window w = hanning(258)[1:-1];
+ *   [256, 768)  the twiddles, cos(2 pi k / 512) at 256 + 2 k and -sin(2 pi k / 512) at
+ *               256 + 2 k + 1, k < 256;
+ *   [768, ...)  hh = up * win, 2 Hl + 1 taps with hh[-Hl] first, win the unit-sum low-pass
+ *               of the resampler (stoi.resample_filter); absent for 1/1.
+ *
+ * Stages, all fp64, every sum in a fixed order, no atomics (two calls on the same inputs
+ * give the same bits; a row's result does not depend on the other rows of the batch):
+ *  1. resampling to 10 kHz by the reduced ratio up/down = 10000 / rate:
+ *     r[k] = sum_i hh[k down - i up + Hl] s[i], k < n10 = ceil(length up / down), i ascending
+ *     over the samples inside the signal, acc = acc + hh s without FMA contraction (the index
+ *     formula of ctn_dmix_mix_sp); 1/1 copies exactly;
+ *  2. frames k < K = (n10 - 256) / 128 + 1 (0 for n10 < 256) of a reference,
+ *     nrm_k = |w r[128 k : 128 k + 256]|_2; frame k is kept iff
+ *     (nrm_k + EPS) * 100 > max_k nrm_k + EPS (EPS = 2^-52), i.e. less than 40 dB below the
+ *     loudest; idx[0 ... kept - 1] are the kept frame numbers, kept[m][j] their count.  The
+ *     mask of reference j is applied to reference j and to every signal scored against it;
+ *  3. frame j < kept of the overlap-add z of the kept windowed frames at hop 128, rebuilt
+ *     from the kept frames idx[j-1], idx[j], idx[j+1] added in that order (z is not stored),
+ *     windowed again, zero-padded to 512; reference and signal as x + i y through one complex
+ *     FFT, split by conjugate symmetry (a frame of all zeros has exactly zero envelopes,
+ *     not the other signal's rounding residue); X[b][j], Y[b][j] = sqrt(sum of |.|^2 over the bins
+ *     [lo_b, hi_b)) of the 15 third-octave bands from 150 Hz, lo = 7 9 11 14 17 22 27 34 43 55
+ *     69 87 109 138 174, hi = lo shifted by one band, then 219;
+ *  4. segments s < J = kept - 29 of 30 frames.  STOI: per band, ys scaled by
+ *     |xs| / (|ys| + EPS), clipped at xs (1 + 10^(15/20)), both mean-subtracted and divided by
+ *     (norm + EPS), their inner products summed over bands and segments and divided by 15 J.
+ *     ESTOI: xs and ys mean-subtracted and divided by (norm + EPS) along the frames, then the
+ *     same along the bands; sum of (xn yn / 30) divided by J;
+ *  5. kept[m][j] < 30: both scores are 1e-5 (pystoi's value) and status[m][j] = 1, else 0.
+ * The call allocates nothing and does not synchronise the host; everything runs on `stream`.
+ * Limits: 1 <= M, E <= 65535; 1 <= C <= 16; T >= 1; 1 <= up, down <= 64 and reduced;
+ * 1 <= Hl <= 4096 unless up = down = 1 (Hl is then ignored); ceil(T up / down) < 2^31;
+ * lengths in [1, T] (a length outside [0, T] is clamped into it on the device).  Beyond a
+ * limit: 0 doubles / 0 workspace bytes / an error code with a ctn_last_error message;
+ * arguments are validated before any device access.
+ * ------------------------------------------------------------------------- */
+typedef struct { int32_t M, C, E, T;   /* T = row stride in samples */
+                 int32_t up, down, Hl; } ctn_stoi_desc;
+size_t ctn_stoi_table_doubles(const ctn_stoi_desc* d);   /* 256 + 512 + (up == down ? 0 : 2 Hl + 1) */
+size_t ctn_stoi_workspace_bytes(const ctn_stoi_desc* d);
+int ctn_stoi_eval(const ctn_stoi_desc* d, const float* refs /*[M][C][T]*/, const float* sigs /*[M][E][T]*/,
+                  const int32_t* lengths /*[M]*/, const double* tab,
+                  double* score /*[M][E][C][2]: STOI, ESTOI*/, int32_t* kept /*[M][C]*/,
+                  int32_t* status /*[M][C]: 1 = fewer than 30 kept frames, score = 1e-5*/,
+                  void* ws, size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
  * Dynamic mixing: training batches drawn and mixed on the device from a resident corpus
  * of single-speaker utterances, instead of the host collation of fixed mixtures
  * (src/data.py:131-159 _collate_fn, :237-271 load_mixtures_and_sources).  Added within ABI v13
