@@ -96,9 +96,11 @@ __global__ __launch_bounds__(256) void pit_final_kernel(PitArgs a) {
     for (int i = 0; i < C; ++i) {
       Ee[i] = v[3 * C + i] - 2.0 * eb[i] * v[i] + n * eb[i] * eb[i];
       Et[i] = v[4 * C + i] - 2.0 * sb[i] * v[C + i] + n * sb[i] * sb[i];
+      // sum (e - eb)(s - sb) = ES - eb SSv - sb (SE - n eb), and SE = n eb: the last term is
+      // left out, not left to cancel (its rounding residue made D, and with it the gradient
+      // of a length-1 row, nonzero once the source sum over all t differs from SSv)
 #pragma unroll
-      for (int j = 0; j < C; ++j)
-        D[i][j] = v[5 * C + i * C + j] - eb[i] * v[C + j] - sb[j] * v[i] + n * eb[i] * sb[j];
+      for (int j = 0; j < C; ++j) D[i][j] = v[5 * C + i * C + j] - eb[i] * v[C + j];
     }
     double snr[C][C], ratio[C][C], Pp[C][C], Ne[C][C];
 #pragma unroll
@@ -292,7 +294,7 @@ __global__ __launch_bounds__(256) void pit_final_wide_kernel(PitArgs a) {
     const double ebi = v[i] / n, sbj = v[2 * C + j] / n;
     const double Ee = v[3 * C + i] - 2.0 * ebi * v[i] + n * ebi * ebi;
     const double Etj = v[4 * C + j] - 2.0 * sbj * v[C + j] + n * sbj * sbj;
-    const double D = v[5 * C + i * C + j] - ebi * v[C + j] - sbj * v[i] + n * ebi * sbj;
+    const double D = v[5 * C + i * C + j] - ebi * v[C + j];   // as pit_final: sb (SE - n eb) = 0 left out
     const double E = Etj + PIT_EPS;
     Pp[i][j] = D * D * Etj / (E * E);
     Ne[i][j] = Ee - 2.0 * D * D / E + D * D * Etj / (E * E);

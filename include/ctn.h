@@ -211,7 +211,10 @@ int ctn_decoder_backward(const ctn_codec_desc* d, const void* x_last, const void
  * permutations (:66) and keeps the first maximum (torch.argmax); 11 <= C <= 16, past what
  * the reference's C!-row one-hot table can hold, solves the same maximum as a linear
  * assignment (Hungarian, fp64) and reports its lexicographic rank in best_perm (exact ties
- * may pick another optimal permutation).  The encoder/decoder descriptors accept 1..16
+ * may pick another optimal permutation).  The backward is one fp32 pass
+ * scale (al s + be e + off), so its relative accuracy degrades in proportion to the
+ * estimate's offset / amplitude (8e-6 of a row's largest gradient at offset 100,
+ * amplitude 1; 3e-7 at offset 0.3).  The encoder/decoder descriptors accept 1..16
  * (streaming: 1..8).
  * ------------------------------------------------------------------------- */
 typedef struct { int32_t M, C, T; } ctn_pit_desc;

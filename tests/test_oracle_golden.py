@@ -1,5 +1,6 @@
 """Pin the CPU oracle (oracle/ctn_oracle.py) against vectors captured from the
 real reference (tests/golden/make_golden.py).  CPU only."""
+import itertools
 import os
 
 import numpy as np
@@ -105,6 +106,34 @@ def test_pit(C, tag):
     close(est_m, g[k + ".est_m"], 0, 0)
     close(reord, g[k + ".reord"], 0, 0)
     close(est.grad, g[k + ".gest"], 1e-4, 1e-7)
+
+
+@pytest.mark.parametrize("C", [1, 2, 4, 7])
+def test_pit_source_nonzero_beyond_length(C):
+    """pit_edges.npz (make_golden_pit_edges.py): the source is NOT zeroed beyond the lengths,
+    so the reference's source mean over all t (pit_criterion.py:42) differs from the mean
+    over t < length; every other PIT fixture has the two equal.  The fp64 reference of
+    tests/test_gpu_pit_edges.py (O.si_snr_pairwise) leans on exactly this."""
+    g = load("pit_edges.npz")
+    k = f"pit.C{C}.nz"
+    src, lens = T(g[k + ".src"]), T(g[k + ".len"])
+    assert all(float(src[b, :, int(l):].abs().max()) > 0 for b, l in enumerate(lens) if l < src.shape[2])
+    est = T(g[k + ".est"]).clone().requires_grad_(True)
+    loss, max_snr, est_m, reord = O.cal_loss(src, est, lens)
+    loss.backward()
+    close(loss, g[k + ".loss"], 1e-5, 1e-5)
+    close(max_snr, g[k + ".max_snr"], 1e-5, 1e-5)
+    close(est_m, g[k + ".est_m"], 0, 0)
+    close(reord, g[k + ".reord"], 0, 0)
+    close(est.grad, g[k + ".gest"], 1e-4, 1e-7)
+    m2, _, idx, _ = O.si_snr_pit(src, T(g[k + ".est"]), lens)
+    close(m2, g[k + ".max_snr"], 1e-5, 1e-5)
+    assert idx.tolist() == g[k + ".idx"].tolist()
+    # the pairwise matrix the GPU edge tests build their fp64 reference from, in fp64
+    snr, _ = O.si_snr_pairwise(src.double(), T(g[k + ".est"]).double(), lens)
+    pm = torch.tensor(list(itertools.permutations(range(C))))[idx]
+    val = torch.stack([snr[b, torch.arange(C), pm[b]].sum() / C for b in range(len(lens))])
+    close(val.view(-1, 1), g[k + ".max_snr"], 1e-5, 1e-5)
 
 
 @pytest.mark.parametrize("C", [9, 10])
