@@ -12,6 +12,8 @@
 // incoming gradient here (bn_apply) and the fused backward runs with zero sums.
 #include <math.h>
 
+#include <type_traits>
+
 #include "ctn_common.h"
 #include "ctn_kernels.h"
 
@@ -43,9 +45,13 @@ __global__ __launch_bounds__(BN_NT) void bn_partials_kernel(BnArgs p) {
       rs[e] = st.y;
     }
   }
-  float s[8], q[8];
+  // MODE 0 accumulates in fp64: the variance is E[x^2] - mean^2, and an fp32 x*x alone
+  // (2^-24 of mean^2) is (mean/std)^2 times that of the variance (2 % at |mean|/std = 500).
+  // An fp32 value's square is exact in fp64.
+  using Acc = typename std::conditional<MODE == 0, double, float>::type;
+  Acc s[8], q[8];
 #pragma unroll
-  for (int e = 0; e < 8; ++e) s[e] = q[e] = 0.f;
+  for (int e = 0; e < 8; ++e) s[e] = q[e] = 0;
   if (rl < nrl) {
     for (int i = rl; i < BN_RPB; i += nrl) {
       const long r = r0 + i;
@@ -55,7 +61,7 @@ __global__ __launch_bounds__(BN_NT) void bn_partials_kernel(BnArgs p) {
       if constexpr (MODE == 0) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
-          const float x = prelu(a[e], al);
+          const double x = prelu(a[e], al);
           s[e] += x;
           q[e] += x * x;
         }
