@@ -503,10 +503,10 @@ static int tb_backward_bn(const ctn_tblock_desc* d, const ctn_tblock_params* p, 
   SlabBatch sb{};
   sb.d[0] = SlabDesc{L.cpart2, gr->w2, L.chunks2, HB, HB};
   sb.d[1] = SlabDesc{L.cpart1, gr->w1, L.chunks1, HB, HB};
-  sb.d[2] = SlabDesc{L.colD, gr->gamma1, dwb, H, dws};
-  sb.d[3] = SlabDesc{L.colD + H, gr->beta1, dwb, H, dws};
-  sb.d[4] = SlabDesc{L.colD + 2 * H, gr->wd, dwb, H * d->P, dws};
-  sb.d[5] = SlabDesc{L.colD + (4 + d->P) * H, gr->alpha2, dwb, 1, dws};
+  sb.d[2] = SlabDesc{L.colD + dw_col_off_gamma1(d->P, H), gr->gamma1, dwb, H, dws};
+  sb.d[3] = SlabDesc{L.colD + dw_col_off_beta1(d->P, H), gr->beta1, dwb, H, dws};
+  sb.d[4] = SlabDesc{L.colD + dw_col_off_wd(d->P, H), gr->wd, dwb, H * d->P, dws};
+  sb.d[5] = SlabDesc{L.colD + dw_col_off_alpha2(d->P, H), gr->alpha2, dwb, 1, dws};
   sb.d[6] = SlabDesc{L.alphaSlab, gr->alpha1, nb, 1, 1};
   sb.nd = 7;
   CTN_HIP(launch_slab_reduce(sb, L.srtmp, s));
@@ -608,12 +608,12 @@ static int tb_grad_slabs(const TbPlan& pl, const TbLayout& L, const ctn_tblock_g
   const int HB = pl.H * pl.B, H = pl.H, P = pl.P;
   out[0] = SlabDesc{L.cpart2, gr->w2, pl.chunks2, HB, HB};
   out[1] = SlabDesc{L.cpart1, gr->w1, pl.chunks1, HB, HB};
-  out[2] = SlabDesc{L.colD + (2 + P) * H, gr->gamma2, dwb, H, dws};
-  out[3] = SlabDesc{L.colD + (3 + P) * H, gr->beta2, dwb, H, dws};
-  out[4] = SlabDesc{L.colD, gr->gamma1, dwb, H, dws};
-  out[5] = SlabDesc{L.colD + H, gr->beta1, dwb, H, dws};
-  out[6] = SlabDesc{L.colD + 2 * H, gr->wd, dwb, H * P, dws};
-  out[7] = SlabDesc{L.colD + (4 + P) * H, gr->alpha2, dwb, 1, dws};
+  out[2] = SlabDesc{L.colD + dw_col_off_gamma2(P, H), gr->gamma2, dwb, H, dws};
+  out[3] = SlabDesc{L.colD + dw_col_off_beta2(P, H), gr->beta2, dwb, H, dws};
+  out[4] = SlabDesc{L.colD + dw_col_off_gamma1(P, H), gr->gamma1, dwb, H, dws};
+  out[5] = SlabDesc{L.colD + dw_col_off_beta1(P, H), gr->beta1, dwb, H, dws};
+  out[6] = SlabDesc{L.colD + dw_col_off_wd(P, H), gr->wd, dwb, H * P, dws};
+  out[7] = SlabDesc{L.colD + dw_col_off_alpha2(P, H), gr->alpha2, dwb, 1, dws};
   out[8] = SlabDesc{L.alphaSlab, gr->alpha1, pl.nalpha, 1, 1};
   return 9;
 }

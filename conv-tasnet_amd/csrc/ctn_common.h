@@ -305,6 +305,11 @@ CTN_DEV float wave_sum_dpp(float v) {
   v += dpp_f<0x143, 0xC>(v);   // row_bcast:31 into rows 2 and 3
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+// a pair held by one lane (wave-uniform index), broadcast with v_readlane
+CTN_DEV float2 readlane2(float2 v, int lane) {
+  return make_float2(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), lane)),
+                     __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), lane)));
+}
 
 // Sum over the four 16-lane rows of a wave (the lanes l, l^16, l^32, l^48) with
 // v_permlane16_swap / v_permlane32_swap: VALU lane exchanges, no LDS instruction
@@ -413,6 +418,26 @@ struct StatFold {
   WsRuns ws;                       // WS run layout when ws.grid > 0
 };
 
+// The one spelling of the statistics finish, in fp64: mode 0 (mean, rstd) with biased
+// variance and eps inside the sqrt, mode 1 (S / cnt, SS / cnt).  Every finalize launch,
+// fold and in-kernel finish goes through it, so they agree bit for bit whatever the
+// compiler contracts (var is an fma of -mean, mean by default).
+CTN_DEV float2 stat_finish(int mode, double s, double ss, double cnt, float eps) {
+  if (mode == 0) {
+    const double mean = s / cnt;
+    double var = ss / cnt - mean * mean;
+    if (var < 0.0) var = 0.0;
+    return make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
+  }
+  return make_float2((float)(s / cnt), (float)(ss / cnt));
+}
+// cLN: the sums of one frame row over its H channels, finished in place (fin) or left as
+// the row's slab entry for a finalize launch
+CTN_DEV void row_stat_store(int mode, float s, float ss, int H, float eps, float2* fin, double2* slab, int row) {
+  if (fin) fin[row] = stat_finish(mode, (double)s, (double)ss, (double)H, eps);
+  else slab[row] = make_double2((double)s, (double)ss);
+}
+
 // Finalize group m, executed by a whole wave: lane l sums the group's partials
 // l, l+64, ... in order, then an xor butterfly (every lane ends with the same
 // bits, addition being commutative).
@@ -462,13 +487,7 @@ CTN_DEV float2 fold_stat(const StatFold& f, int m) {
   }
   s = wave_sum(s);
   ss = wave_sum(ss);
-  if (f.mode == 0) {
-    const double mean = s / f.cnt;
-    double var = ss / f.cnt - mean * mean;
-    if (var < 0.0) var = 0.0;
-    return make_float2((float)mean, (float)(1.0 / sqrt(var + (double)f.eps)));
-  }
-  return make_float2((float)(s / f.cnt), (float)(ss / f.cnt));
+  return stat_finish(f.mode, s, ss, f.cnt, f.eps);
 }
 
 // ---------------------------------------------------------------------------

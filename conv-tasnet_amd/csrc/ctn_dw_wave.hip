@@ -39,11 +39,7 @@ CTN_DEV WItem witem(const DwArgs& a, const CombGeom& gm) {
   WItem it;
   it.m = (int)blockIdx.x / gm.wgpu;
   it.wgi = (int)blockIdx.x % gm.wgpu;
-  const int id = it.wgi * gm.ipw + wv;   // ipw = 4: one item per wave
-  const bool active = id < gm.items;
-  it.rho = active ? id / gm.nseg : 0;
-  it.j0 = active ? (id % gm.nseg) * a.seg : 0;
-  it.j1 = active ? min(it.j0 + a.seg, gm.jmax) : it.j0;
+  comb_segment(a, gm, it.wgi * gm.ipw + wv, it.rho, it.j0, it.j1);   // ipw = 4: one item per wave
   it.base = it.m * a.g.Kp;
   return it;
 }
@@ -128,11 +124,7 @@ __global__ __launch_bounds__(256, 4) void dw_fwd_wave_kernel(DwArgs a) {
     bst = nst;
     batch_fetch(bbase + CB);
   };
-  auto bcast = [&](float2 v, int j) {
-    const int l = j - bbase;
-    return make_float2(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), l)),
-                       __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), l)));
-  };
+  auto bcast = [&](float2 v, int j) { return readlane2(v, j - bbase); };
   // n1 of one row (EDGE: 0 outside the utterance, a select, so a non-finite value in the
   // row it fetched cannot leak in)
   auto finish = [&](auto edge, const v4u& vh, bool ok, float2 st, float* out) __attribute__((always_inline)) {
@@ -161,17 +153,7 @@ __global__ __launch_bounds__(256, 4) void dw_fwd_wave_kernel(DwArgs a) {
   RowPark pk;
   pk.j0 = it.j0;
   auto park_flush = [&](int n) {   // final (mean, rstd) or the (sum, sum sq) slab entry
-    const int k = it.rho + (pk.j0 + lane) * dil;
-    if (lane < n && k < Kp) {
-      if (a.st2_out) {   // the arithmetic of stats_finalize (mode 0)
-        const double mean = (double)pk.s / H;
-        double var = (double)pk.ss / H - mean * mean;
-        if (var < 0.0) var = 0.0;
-        a.st2_out[it.base + k] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)a.eps)));
-      } else {
-        a.slab2[it.base + k] = make_double2((double)pk.s, (double)pk.ss);
-      }
-    }
+    pk.flush(n, lane, it.rho, dil, Kp, it.base, 0, H, a.eps, a.st2_out, a.slab2);
   };
   auto step = [&](auto edge, auto qc, int j, const v4u& vh) __attribute__((always_inline)) {
     constexpr bool EDGE = decltype(edge)::value;
@@ -201,11 +183,7 @@ __global__ __launch_bounds__(256, 4) void dw_fwd_wave_kernel(DwArgs a) {
       ts += s;
       tss += ss;
     } else {
-      s = wave_sum_dpp(s);
-      ss = wave_sum_dpp(ss);
-      const int pq = j - pk.j0;
-      pk.s = lane == pq ? s : pk.s;
-      pk.ss = lane == pq ? ss : pk.ss;
+      pk.put(lane, j, wave_sum_dpp(s), wave_sum_dpp(ss));
     }
   };
   auto boundary = [&]() {
@@ -405,11 +383,7 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
     bst1 = nst1;
     batch_fetch(bbase + CB);
   };
-  auto bcast = [&](float2 v, int j) {
-    const int l = j - bbase;
-    return make_float2(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), l)),
-                       __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), l)));
-  };
+  auto bcast = [&](float2 v, int j) { return readlane2(v, j - bbase); };
 
   // gd window: G-step s in slot (s - j0 - GT) mod 3, so at walk step j (q = (j - j0) mod 3)
   // the gd of row j + POWN - t (tap t) sits in slot (q + 3 - t) mod 3, the newest in q
@@ -483,14 +457,8 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
 
   RowPark pk;
   pk.j0 = it.j0;
-  auto park_flush = [&](int n) {
-    const int k = it.rho + (pk.j0 + lane) * dil;
-    if (lane < n && k < Kp) {
-      if (a.sm1_out)   // the arithmetic of stats_finalize (mode 1)
-        a.sm1_out[it.base + k] = make_float2((float)((double)pk.s / H), (float)((double)pk.ss / H));
-      else
-        a.slab1[it.base + k] = make_double2((double)pk.s, (double)pk.ss);
-    }
+  auto park_flush = [&](int n) {   // final norm-1 backward means or the slab entry
+    pk.flush(n, lane, it.rho, dil, Kp, it.base, 1, H, a.eps, a.sm1_out, a.slab1);
   };
 
   // one walk step with its operands in r; q = (j - j0) mod 3 picks the window slots
@@ -553,11 +521,7 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
       ts += s;
       tss += ss;
     } else {   // parked in lane j - pk.j0 (flushed at batch boundaries: pk.j0 == bbase)
-      s = wave_sum_dpp(s);
-      ss = wave_sum_dpp(ss);
-      const int pq = j - pk.j0;
-      pk.s = lane == pq ? s : pk.s;
-      pk.ss = lane == pq ? ss : pk.ss;
+      pk.put(lane, j, wave_sum_dpp(s), wave_sum_dpp(ss));
     }
   };
   auto boundary = [&]() {   // cLN: the walk reached bbase + CB
@@ -619,33 +583,8 @@ __global__ __launch_bounds__(256, 2) void dw_bwd_wave_kernel(DwArgs a) {
     if (it.j1 > pk.j0) park_flush(it.j1 - pk.j0);
 
   // ---- workgroup reductions: column partials, alpha2, norm1 sums (dw_bwd_kernel's order)
-  constexpr int cgn = 64, nrl = 4;
-  const int rl = threadIdx.x >> 6;
-  float* cs = a.col_slab + (size_t)blockIdx.x * dw_col_stride(a);
-  col_reduce8(buf, cgam, rl, lane, nrl, cgn, true, cs);
-  col_reduce8(buf, cbet, rl, lane, nrl, cgn, true, cs + H);
-  col_reduce8(buf, cgam2, rl, lane, nrl, cgn, true, cs + (2 + P) * H);
-  col_reduce8(buf, cbet2, rl, lane, nrl, cgn, true, cs + (3 + P) * H);
-#pragma unroll
-  for (int t = 0; t < P; ++t) {   // stored [H][P] to match the parameter layout [H,1,P]
-#pragma unroll
-    for (int e = 0; e < 8; ++e) buf[rl * H + lane * 8 + e] = cwd[t][e];
-    __syncthreads();
-    for (int chn = threadIdx.x; chn < H; chn += blockDim.x) {
-      float sacc = 0.f;
-      for (int u = 0; u < nrl; ++u) sacc += buf[u * H + chn];
-      cs[2 * H + chn * P + t] = sacc;
-    }
-    __syncthreads();
-  }
-  {
-    double v3[3] = {(double)calpha, (double)ts, (double)tss};
-    block_sum_d<3>(v3, red);
-    if (threadIdx.x == 0) {
-      cs[(4 + P) * H] = (float)v3[0];
-      if constexpr (NK == NORM_GLN) a.slab1[(size_t)it.m * gm.wgpu + it.wgi] = make_double2(v3[1], v3[2]);
-    }
-  }
+  dw_bwd_tail<P>(a, buf, red, cgam, cbet, cgam2, cbet2, cwd, calpha, ts, tss, threadIdx.x >> 6, lane, 4, 64, H,
+                 NK == NORM_GLN ? (long)it.m * gm.wgpu + it.wgi : -1L);
 }
 
 }  // namespace
@@ -660,34 +599,31 @@ bool dw_wave_enabled() {
 bool dw_wave_eligible(DType dt, const DwArgs& a) {
   if (dt != BF16 || a.H != WV_H || a.P != WV_P || !dw_wave_enabled()) return false;
   if (a.g.rows() * WV_H * 2 > 0x7fffffffL) return false;   // 32-bit buffer offsets
-  const int pown = a.pad / a.dil;
-  return pown * a.dil == a.pad && (pown == a.P - 1 || pown == (a.P - 1) / 2);
+  return dw_pown(a) >= 0;
 }
 
-hipError_t launch_dw_fwd_wave(const DwArgs& a, hipStream_t s) {
-  const bool causal = a.pad / a.dil == WV_P - 1;
+namespace {
+struct WaveFwd {
+  template <int NK, bool C> static constexpr auto kernel = dw_fwd_wave_kernel<NK, C>;
+};
+struct WaveBwd {
+  template <int NK, bool C> static constexpr auto kernel = dw_bwd_wave_kernel<NK, C>;
+};
+template <class K> hipError_t dw_wave_launch(const DwArgs& a, hipStream_t s) {
+  const bool causal = dw_causal(dw_pown(a), WV_P);
   const dim3 grid(dw_blocks(a)), blk(256);
   if (a.norm == NORM_GLN) {
-    if (causal) hipLaunchKernelGGL((dw_fwd_wave_kernel<NORM_GLN, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((dw_fwd_wave_kernel<NORM_GLN, false>), grid, blk, 0, s, a);
+    if (causal) hipLaunchKernelGGL((K::template kernel<NORM_GLN, true>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((K::template kernel<NORM_GLN, false>), grid, blk, 0, s, a);
   } else {
-    if (causal) hipLaunchKernelGGL((dw_fwd_wave_kernel<NORM_CLN, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((dw_fwd_wave_kernel<NORM_CLN, false>), grid, blk, 0, s, a);
+    if (causal) hipLaunchKernelGGL((K::template kernel<NORM_CLN, true>), grid, blk, 0, s, a);
+    else hipLaunchKernelGGL((K::template kernel<NORM_CLN, false>), grid, blk, 0, s, a);
   }
   return hipGetLastError();
 }
+}  // namespace
 
-hipError_t launch_dw_bwd_wave(const DwArgs& a, hipStream_t s) {
-  const bool causal = a.pad / a.dil == WV_P - 1;
-  const dim3 grid(dw_blocks(a)), blk(256);
-  if (a.norm == NORM_GLN) {
-    if (causal) hipLaunchKernelGGL((dw_bwd_wave_kernel<NORM_GLN, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((dw_bwd_wave_kernel<NORM_GLN, false>), grid, blk, 0, s, a);
-  } else {
-    if (causal) hipLaunchKernelGGL((dw_bwd_wave_kernel<NORM_CLN, true>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((dw_bwd_wave_kernel<NORM_CLN, false>), grid, blk, 0, s, a);
-  }
-  return hipGetLastError();
-}
+hipError_t launch_dw_fwd_wave(const DwArgs& a, hipStream_t s) { return dw_wave_launch<WaveFwd>(a, s); }
+hipError_t launch_dw_bwd_wave(const DwArgs& a, hipStream_t s) { return dw_wave_launch<WaveBwd>(a, s); }
 
 }  // namespace ctn

@@ -513,7 +513,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
     store_out(t);
   };
   // cLN: final (mean, rstd) of tile t's rows from the WV wave partials, summed in wave
-  // order in fp64 (the arithmetic of stats_finalize over this layout's parts)
+  // order in fp64 (stat_finish over this layout's parts, as the finalize launch)
   auto cln_final = [&](int t) __attribute__((always_inline)) {
     if constexpr (CLN_FIN) {
       if (p.stats_out && tid < TM) {
@@ -524,10 +524,7 @@ __global__ __launch_bounds__(64 * WV, (S == 2 ? 2 : 1) * WV / 4) void gemm_ws_ke
           sm += v.x;
           sq += v.y;
         }
-        const double mean = sm / p.Nout;
-        double var = sq / p.Nout - mean * mean;
-        if (var < 0.0) var = 0.0;
-        p.stats_out[(size_t)t * TM + tid] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)p.eps)));
+        p.stats_out[(size_t)t * TM + tid] = stat_finish(0, sm, sq, (double)p.Nout, p.eps);
       }
     }
   };

@@ -217,6 +217,12 @@ int ew_blocks(const DwArgs& a);        // norm1_bwd (128-row blocks)
 int dw_parts_per_group(const DwArgs& a);   // slab parts per utterance (gLN) or per row (cLN)
 // col_slab part layout: [ggamma1 H][gbeta1 H][gwd H*P][ggamma2 H][gbeta2 H][galpha2 1], padded to 4
 __host__ __device__ inline int dw_col_stride(const DwArgs& a) { return ((4 + a.P) * a.H + 1 + 3) & ~3; }
+__host__ __device__ inline int dw_col_off_gamma1(int P, int H) { return 0; }
+__host__ __device__ inline int dw_col_off_beta1(int P, int H) { return H; }
+__host__ __device__ inline int dw_col_off_wd(int P, int H) { return 2 * H; }   // [H][P], as the parameter [H,1,P]
+__host__ __device__ inline int dw_col_off_gamma2(int P, int H) { return (2 + P) * H; }
+__host__ __device__ inline int dw_col_off_beta2(int P, int H) { return (3 + P) * H; }
+__host__ __device__ inline int dw_col_off_alpha2(int P, int H) { return (4 + P) * H; }
 hipError_t launch_dw_fwd(DType dt, const DwArgs& a, hipStream_t s);
 hipError_t launch_dw_bwd(DType dt, const DwArgs& a, hipStream_t s);
 hipError_t launch_norm1_bwd(DType dt, const DwArgs& a, hipStream_t s);

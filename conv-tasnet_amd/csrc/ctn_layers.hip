@@ -46,12 +46,7 @@ __global__ __launch_bounds__(LY_NT) void ln_row_stats_kernel(const T* x, int C, 
   }
   s = wave_sum(s);
   ss = wave_sum(ss);
-  if (lane == 0) {
-    const double mean = s / C;
-    double var = ss / C - mean * mean;
-    if (var < 0.0) var = 0.0;
-    stats[row] = make_float2((float)mean, (float)(1.0 / sqrt(var + (double)eps)));
-  }
+  if (lane == 0) stats[row] = stat_finish(0, s, ss, (double)C, eps);
 }
 
 // gLN: block (m, b) sums rows [b*LY_RB, +LY_RB) of utterance m (valid frames only)
