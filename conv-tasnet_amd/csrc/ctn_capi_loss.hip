@@ -1,7 +1,9 @@
-// C-ABI entries of PIT SI-SNR loss and BSS Eval energies (include/ctn.h ctn_pit_*, ctn_bss_*).
+// C-ABI entries of PIT SI-SNR loss, MixIT loss and BSS Eval energies (include/ctn.h ctn_pit_*,
+// ctn_mixit_*, ctn_bss_*).
 #include "ctn_capi_util.h"
 #include "ctn_bss.h"
 #include "ctn_codec.h"
+#include "ctn_mixit.h"
 
 using namespace ctn;
 
@@ -69,6 +71,61 @@ extern "C" int ctn_pit_backward(const ctn_pit_desc* d, const float* source, cons
   a.src = source; a.est = est; a.lengths = lengths; a.coef = const_cast<float*>(coef);
   a.g_loss = g_loss; a.g_maxsnr = g_max_snr; a.gest = g_est;
   CTN_HIP(launch_pit_backward(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+// ===========================================================================
+// MixIT loss, ctn_mixit.hip (the chunk rule of the PIT statistics)
+// ===========================================================================
+static int mixit_check(const ctn_mixit_desc* d) {
+  if (!d) return fail(CTN_ERR_ARG, "null descriptor");
+  if (d->M < 1 || d->T < 1) return fail(CTN_ERR_ARG, "bad MixIT descriptor M=%d T=%d (both >= 1)", d->M, d->T);
+  if (d->C < MIXIT_CMIN || d->C > MIXIT_CMAX)
+    return fail(CTN_ERR_UNSUPPORTED, "MixIT with C=%d outputs (%d to %d)", d->C, MIXIT_CMIN, MIXIT_CMAX);
+  if (d->mode != CTN_MIXIT_SNR && d->mode != CTN_MIXIT_SI_SNR)
+    return fail(CTN_ERR_ARG, "unknown MixIT mode %d (0 snr, 1 si_snr)", d->mode);
+  if (!isfinite(d->snr_max)) return fail(CTN_ERR_ARG, "MixIT snr_max is not finite");
+  return CTN_OK;
+}
+
+static MixitArgs mixit_args(const ctn_mixit_desc* d) {
+  MixitArgs a{};
+  a.M = d->M; a.C = d->C; a.T = d->T; a.mode = d->mode;
+  a.tau = pow(10.0, -(double)d->snr_max / 10.0);
+  a.chunks = pit_chunks(d->T);
+  return a;
+}
+
+extern "C" size_t ctn_mixit_workspace_bytes(const ctn_mixit_desc* d) {
+  if (mixit_check(d) != CTN_OK) return 0;
+  return (size_t)d->M * pit_chunks(d->T) * mixit_nv(d->C) * sizeof(double) + (size_t)d->M * sizeof(double) + 256;
+}
+
+extern "C" int ctn_mixit_forward(const ctn_mixit_desc* d, const float* mixtures, const float* est,
+                                 const int64_t* lengths, float* loss, float* max_snr, int64_t* assign, float* remix,
+                                 float* coef, void* ws, size_t ws_bytes, void* stream) {
+  if (int rc = mixit_check(d)) return rc;
+  if (!mixtures || !est || !lengths || !loss || !max_snr || !assign || !coef) return fail(CTN_ERR_ARG, "null pointer");
+  if (!ws || ws_bytes < ctn_mixit_workspace_bytes(d)) return fail(CTN_ERR_WORKSPACE, "MixIT workspace too small");
+  MixitArgs a = mixit_args(d);
+  a.mix = mixtures; a.est = est; a.lengths = lengths;
+  a.slab = reinterpret_cast<double*>(ws);
+  a.msd = a.slab + (size_t)d->M * a.chunks * mixit_nv(d->C);
+  a.loss = loss; a.max_snr = max_snr; a.assign = assign; a.coef = coef; a.remix = remix;
+  CTN_HIP(launch_mixit_forward(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
+extern "C" int ctn_mixit_backward(const ctn_mixit_desc* d, const float* mixtures, const float* est,
+                                  const int64_t* lengths, const int64_t* assign, const float* coef,
+                                  const float* g_loss, const float* g_max_snr, float* g_est, void* stream) {
+  if (int rc = mixit_check(d)) return rc;
+  if (!mixtures || !est || !lengths || !assign || !coef || !g_est) return fail(CTN_ERR_ARG, "null pointer");
+  MixitArgs a = mixit_args(d);
+  a.mix = mixtures; a.est = est; a.lengths = lengths;
+  a.assign = const_cast<int64_t*>(assign); a.coef = const_cast<float*>(coef);
+  a.g_loss = g_loss; a.g_maxsnr = g_max_snr; a.gest = g_est;
+  CTN_HIP(launch_mixit_backward(a, (hipStream_t)stream));
   return CTN_OK;
 }
 

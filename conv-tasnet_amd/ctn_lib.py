@@ -68,6 +68,14 @@ class PitDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("M", "C", "T")]
 
 
+MIXIT_SNR, MIXIT_SI_SNR = 0, 1
+
+
+class MixitDesc(ctypes.Structure):
+    """ctn_mixit_desc (include/ctn.h): MixIT loss; mode MIXIT_SNR / MIXIT_SI_SNR."""
+    _fields_ = [(n, c_int32) for n in ("M", "C", "T", "mode")] + [("snr_max", ctypes.c_float)]
+
+
 class BssDesc(ctypes.Structure):
     """ctn_bss_desc (include/ctn.h, ABI v13); T is the row stride in samples."""
     _fields_ = [(n, c_int32) for n in ("M", "C", "E", "T", "flen")]
@@ -179,6 +187,9 @@ _SIGS = {
     "ctn_pit_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_pit_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "ctn_pit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p]),
+    "ctn_mixit_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_mixit_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_mixit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p]),
     "ctn_bss_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_bss_eval": (ctypes.c_int, [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
     "ctn_stoi_table_doubles": (c_size_t, [c_void_p]),

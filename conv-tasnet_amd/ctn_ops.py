@@ -667,6 +667,67 @@ class PITFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
+# MixIT loss (ctn_mixit.hip; include/ctn.h ctn_mixit_*)
+# ----------------------------------------------------------------------------
+MIXIT_MODES = {"snr": L.MIXIT_SNR, "si_snr": L.MIXIT_SI_SNR}
+
+
+class MixITFn(torch.autograd.Function):
+    """(mixtures [M,2,T], est [M,C,T], lengths, mode, snr_max) -> (loss, max_snr [M,1],
+    assign [M], remix [M,2,T]); nothing is masked in place.  mode: "snr" or "si_snr"."""
+
+    @staticmethod
+    def forward(ctx, mixtures, est, lengths, mode="snr", snr_max=30.0):
+        lib = L.load()
+        L.require_device(est, "cal_mixit_loss")
+        if mode not in MIXIT_MODES:
+            raise ValueError(f"MixIT loss {mode!r}: one of {sorted(MIXIT_MODES)}")
+        if est.dim() != 3 or mixtures.dim() != 3 or mixtures.size(1) != 2 or \
+                (mixtures.size(0), mixtures.size(2)) != (est.size(0), est.size(2)):
+            raise ValueError(f"MixIT: mixtures {tuple(mixtures.shape)} must be [M, 2, T] for estimates "
+                             f"{tuple(est.shape)} [M, C, T]")
+        if est.dtype != torch.float32 or not est.is_contiguous():
+            raise L.CtnLibraryError("estimate_source must be a contiguous float32 tensor")
+        mixtures = _f32(mixtures.to(est.device))
+        lengths = lengths.to(device=est.device, dtype=torch.int64).contiguous()
+        M, C, T = est.shape
+        desc = L.MixitDesc(M, C, T, MIXIT_MODES[mode], float(snr_max))
+        nb = lib.ctn_mixit_workspace_bytes(ctypes.byref(desc))
+        if nb == 0:
+            raise L.CtnLibraryError("MixIT: " + lib.ctn_last_error().decode(errors="replace"))
+        dev = est.device
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        max_snr = torch.empty(M, 1, dtype=torch.float32, device=dev)
+        assign = torch.empty(M, dtype=torch.int64, device=dev)
+        coef = torch.empty(M, 2, 4, dtype=torch.float32, device=dev)
+        remix = torch.empty(M, 2, T, dtype=torch.float32, device=dev)
+        ws = L.workspace(nb, dev)
+        L.check(lib.ctn_mixit_forward(ctypes.byref(desc), mixtures.data_ptr(), est.data_ptr(), lengths.data_ptr(),
+                                      loss.data_ptr(), max_snr.data_ptr(), assign.data_ptr(), remix.data_ptr(),
+                                      coef.data_ptr(), ws.data_ptr(), nb, L.stream_handle(dev)), "ctn_mixit_forward")
+        ctx.mark_non_differentiable(assign, remix)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(mixtures, est, lengths, assign, coef)
+        ctx.desc = (M, C, T, MIXIT_MODES[mode], float(snr_max))
+        return loss, max_snr, assign, remix
+
+    @staticmethod
+    def backward(ctx, g_loss, g_max_snr, _g_assign, _g_remix):
+        lib = L.load()
+        mixtures, est, lengths, assign, coef = ctx.saved_tensors
+        M = ctx.desc[0]
+        desc = L.MixitDesc(*ctx.desc)
+        dev = est.device
+        g_est = torch.empty_like(est)
+        gl = _f32(g_loss.reshape(1)) if g_loss is not None else torch.zeros(1, device=dev)
+        gm = _f32(g_max_snr.reshape(M)) if g_max_snr is not None else None
+        L.check(lib.ctn_mixit_backward(ctypes.byref(desc), mixtures.data_ptr(), est.data_ptr(), lengths.data_ptr(),
+                                       assign.data_ptr(), coef.data_ptr(), gl.data_ptr(), L.ptr(gm),
+                                       g_est.data_ptr(), L.stream_handle(dev)), "ctn_mixit_backward")
+        return None, g_est, None, None, None
+
+
+# ----------------------------------------------------------------------------
 # stand-alone separator layers on frame rows (ctn_layers.hip; include/ctn.h ABI v4):
 # the module forwards of TemporalConvNet / DepthwiseSeparableConv / gLN / cLN when
 # they are called on their own (conv_tasnet.py:192-209, 265-272, 319-329, 344-355)

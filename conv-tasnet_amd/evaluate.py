@@ -26,7 +26,11 @@ Same flags and printout as the reference.  Differences, each deliberate:
   §23), so that the cost of windowing in SI-SNRi can be measured on a manifest;
 * ``--cal_stoi 1`` (default 0: nothing changes) also scores STOI and ESTOI of a whole minibatch
   on the device (``cal_STOI_batch``, stoi.py, csrc/ctn_stoi.hip), for the
-  paired estimates and for the unprocessed mixture; the reference has no such option.
+  paired estimates and for the unprocessed mixture; the reference has no such option;
+* ``--mixit_remix 1`` (default 0: nothing changes) scores a MixIT-trained model, which has
+  more outputs than the mixture has sources: its outputs are remixed to the two sources by
+  the best assignment (``mixit_criterion.cal_mixit_loss``, csrc/ctn_mixit.hip)
+  and the remixed pair takes the place of the PIT-paired estimates in every metric.
 """
 import argparse
 
@@ -63,6 +67,13 @@ parser.add_argument('--chunk_overlap_s', default=None, type=float,
                     help='Overlap of neighbouring windows in seconds (default: half of --chunk_s)')
 parser.add_argument('--cal_stoi', default=0, type=int,
                     help='1: also compute STOI and ESTOI on the device (estimates and mixture, batched HIP kernels)')
+parser.add_argument('--mixit_remix', default=0, type=int,
+                    help='1: a MixIT-trained model with more outputs than sources: remix its outputs to the two '
+                         'sources by the best assignment (batched HIP kernels) before they are scored')
+parser.add_argument('--mixit_loss', default='snr', type=str, choices=['snr', 'si_snr'],
+                    help='Score that picks the assignment of --mixit_remix 1')
+parser.add_argument('--mixit_snr_max', default=30.0, type=float,
+                    help='Soft SNR ceiling in dB of --mixit_loss snr')
 
 
 def reorder_inverse(est, source, lengths):
@@ -116,6 +127,14 @@ class Evaluator:
     def _separate(self, mixture, lengths, source):
         """-> estimates paired with the targets (the reference's reorder, or --pit_fix)."""
         est = self._forward(mixture, lengths)                       # [B, C, T]
+        if getattr(self.args, 'mixit_remix', 0):
+            # a MixIT model has more outputs than sources: remix[b, n] is the sum of the outputs
+            # that the best assignment gives to source n, already paired with it
+            from mixit_criterion import cal_mixit_loss
+            if source.size(1) != 2:
+                raise ValueError("--mixit_remix 1 remixes to two sources per mixture, got %d" % source.size(1))
+            return cal_mixit_loss(source, est.contiguous(), lengths, getattr(self.args, 'mixit_loss', 'snr'),
+                                  getattr(self.args, 'mixit_snr_max', 30.0))[3]
         _, _, est, paired = cal_loss(source, est, lengths)
         if self.args.pit_fix:
             paired = reorder_inverse(est, source, lengths)

@@ -95,6 +95,10 @@ class Solver(object):
         self.save_folder, self.model_path = args.save_folder, args.model_path
         self.checkpoint, self.continue_from = args.checkpoint, args.continue_from
         self.print_freq = args.print_freq
+        # --loss mixit (mixit_criterion.py); args written before the flag existed mean pit
+        self.mixit = getattr(args, 'loss', 'pit') == 'mixit'
+        self.mixit_loss = getattr(args, 'mixit_loss', 'snr')
+        self.mixit_snr_max = getattr(args, 'mixit_snr_max', 30.0)
         self.schedule = PlateauSchedule(bool(args.half_lr), bool(args.early_stop))
         self.tr_loss = torch.zeros(self.epochs)
         self.cv_loss = torch.zeros(self.epochs)
@@ -196,6 +200,21 @@ class Solver(object):
             return batch
         return tuple(t.to(dev, non_blocking=True) for t in batch)
 
+    def _loss(self, model, mixture, lengths, source, cross_valid):
+        """The loss of one batch: PIT against the sources, or, with --loss mixit, MixIT."""
+        if not self.mixit:
+            return cal_loss(source, model(mixture), lengths)[0]
+        from mixit_criterion import cal_mixit_loss, mom_pairs
+        if cross_valid:
+            # remix evaluation: the model's outputs remixed to the two true sources
+            if source.size(1) != 2:
+                raise ValueError("--loss mixit validates against two sources per mixture, got %d" % source.size(1))
+            refs, lens = source, lengths
+        else:
+            # utterances 2m and 2m+1 become one mixture of mixtures; the sources are not used
+            mixture, refs, lens = mom_pairs(mixture, lengths)
+        return cal_mixit_loss(refs, model(mixture), lens, self.mixit_loss, self.mixit_snr_max)[0]
+
     def _run_one_epoch(self, epoch, cross_valid=False):
         """One pass over the train (or cv) loader -> mean loss over all ranks (solver.py:158-210)."""
         loader = self.cv_loader if cross_valid else self.tr_loader
@@ -212,9 +231,9 @@ class Solver(object):
                 # the unwrapped module: a DDP forward would broadcast buffers (BN running
                 # stats), a collective that ranks without a cv minibatch never join
                 with torch.no_grad():
-                    loss = cal_loss(source, _inner(self.model)(mixture), lengths)[0]
+                    loss = self._loss(_inner(self.model), mixture, lengths, source, True)
             else:
-                loss = cal_loss(source, self.model(mixture), lengths)[0]
+                loss = self._loss(self.model, mixture, lengths, source, False)
                 self.optimizer.zero_grad()
                 loss.backward()
                 if getattr(self.model, "grad_sync", None) is not None:   # train.FlatDP

@@ -25,7 +25,14 @@ Differences, each deliberate:
   of wav files) add reverberation and noise on the GPU: every source is convolved with a drawn
   room impulse response (probability ``--dm_rir_prob``; responses longer than
   ``--dm_rir_max_taps`` are truncated) and every mixture gets a drawn noise segment at an SNR
-  from ``--dm_snr_db LO HI``.  Cross validation keeps the fixed set.
+  from ``--dm_snr_db LO HI``.  Cross validation keeps the fixed set;
+* ``--loss mixit`` (default ``pit``: nothing changes) trains without isolated sources
+  (mixit_criterion.py): utterances 2m and 2m+1 of every training batch are
+  added into one mixture of mixtures, the model separates it into ``--C`` outputs (2 to 8) and
+  the MixIT loss (``--mixit_loss snr|si_snr``, ``--mixit_snr_max``) scores the best remix
+  against the two mixtures; ``--batch_size`` must be even.  With ``--dynamic_mix 1`` the mixer
+  draws ``--mixit_speakers`` speakers per single mixture.  Cross validation remixes the
+  outputs to the two sources of each validation mixture.
 """
 import argparse
 import os
@@ -151,6 +158,42 @@ parser.add_argument('--dm_noise_dir', default='', type=str,
 parser.add_argument('--dm_snr_db', default=[-5.0, 5.0], type=float, nargs=2, metavar=('LO', 'HI'),
                     help='Range of the uniform draw of the clean mixture to noise ratio (dB)')
 
+# MixIT (mixit_criterion.py); pit: the reference's loss on isolated sources
+parser.add_argument('--loss', default='pit', type=str, choices=['pit', 'mixit'],
+                    help='pit: PIT SI-SNR against the sources.  mixit: mixture-invariant training, every two '
+                         'utterances of a batch are added into one mixture of mixtures and --C is the number of '
+                         'model outputs; the sources are not used')
+parser.add_argument('--mixit_loss', default='snr', type=str, choices=['snr', 'si_snr'],
+                    help='MixIT score: snr (thresholded at --mixit_snr_max) or si_snr')
+parser.add_argument('--mixit_snr_max', default=30.0, type=float,
+                    help='MixIT soft SNR ceiling in dB (snr only)')
+parser.add_argument('--mixit_speakers', default=2, type=int,
+                    help='Speakers the dynamic mixer draws per single mixture under --loss mixit')
+
+
+def check_mixit(args):
+    """--loss mixit pairs the utterances of a batch and needs at least two model outputs."""
+    import math
+    if args.loss != 'mixit':
+        return
+    if args.batch_size < 2 or args.batch_size % 2:
+        raise ValueError(f"--loss mixit adds utterances 2m and 2m+1 of a batch into one mixture of mixtures: "
+                         f"--batch_size {args.batch_size} must be even")
+    if not 2 <= args.C <= 8:
+        raise ValueError(f"--loss mixit: --C {args.C} is the number of model outputs, 2 to 8")
+    if not math.isfinite(args.mixit_snr_max):
+        raise ValueError(f"--mixit_snr_max {args.mixit_snr_max}: a finite value in dB")
+    if args.mixit_speakers < 1:
+        raise ValueError(f"--mixit_speakers {args.mixit_speakers}: at least 1")
+
+
+def minibatch_rows(mb):
+    """Rows of the batch that data.py cuts from one AudioDataset minibatch entry
+    [utterances, *speakers, sample_rate, segment_len]: ceil(samples / segment_len) per utterance."""
+    import math
+    seg = mb[-1]
+    return len(mb[0]) if seg < 0 else sum(math.ceil(int(u[1]) / seg) for u in mb[0])
+
 
 def check_dm_speeds(args):
     """--dm_speeds needs --dynamic_mix 1 and percents the resampler supports."""
@@ -197,7 +240,9 @@ def dynamic_mix_loader(args, static_loader, rank, world):
         if rank == 0:
             print("Dynamic mixing: {} noise recordings ({:.1f} MB on the device)".format(noise.n_utts,
                                                                                        noise.nbytes / 1e6))
-    mixer = DynamicMixer(corpus, args.batch_size, args.C, int(args.segment * args.sample_rate), seed=args.dm_seed,
+    # under MixIT --C counts the model's outputs, not the speakers of a single mixture
+    speakers = args.mixit_speakers if getattr(args, 'loss', 'pit') == 'mixit' else args.C
+    mixer = DynamicMixer(corpus, args.batch_size, speakers, int(args.segment * args.sample_rate), seed=args.dm_seed,
                          level_mode=args.dm_level_mode, level_db=tuple(args.dm_level_db), peak=args.dm_peak,
                          rank=rank, world=world, speeds=args.dm_speeds, rirs=rirs, rir_prob=args.dm_rir_prob,
                          noise=noise, snr_db=tuple(args.dm_snr_db))
@@ -232,6 +277,7 @@ class FlatDP(Single):
 
 
 def main(args):
+    check_mixit(args)
     check_dm_speeds(args)
     check_dm_aug(args)
     if args.dynamic_mix and not args.use_cuda:
@@ -245,6 +291,10 @@ def main(args):
     # data
     tr_dataset = AudioDataset(args.train_dir, args.batch_size,
                               sample_rate=args.sample_rate, segment=args.segment)
+    if args.loss == 'mixit':
+        # a leftover minibatch of one utterance cannot form a mixture of mixtures; dropped here,
+        # before the sampler shares the minibatches out, so every rank runs the same steps
+        tr_dataset.minibatch = [mb for mb in tr_dataset.minibatch if minibatch_rows(mb) >= 2]
     cv_dataset = AudioDataset(args.valid_dir, batch_size=1,  # 1 -> use less GPU memory to do cv
                               sample_rate=args.sample_rate,
                               segment=-1, cv_maxlen=args.cv_maxlen)  # -1 -> use full audio

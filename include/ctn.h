@@ -226,6 +226,43 @@ int ctn_pit_backward(const ctn_pit_desc* d, const float* source, const float* es
                      const float* coef, const float* g_loss, const float* g_max_snr, float* g_est, void* stream);
 
 /* -------------------------------------------------------------------------
+ * MixIT loss (mixture-invariant training, Wisdom et al. 2020): the model separates a
+ * mixture of two recordings into C outputs; every output is assigned to one of the two
+ * recordings, and the two remixed sums are scored against the recordings under the best
+ * assignment.  Added within ABI v13 without a version bump (nothing existing changed):
+ * callers probe for the symbol.  No reference counterpart (src/pit_criterion.py needs
+ * isolated sources); DESIGN.md §27 has the full definition.
+ *
+ * mixtures [M][2][T], est [M][C][T] fp32 contiguous, 2 <= C <= 8, lengths [M] (>= 1; values
+ * above T count as T).  All sums run over t < lengths[m]; nothing is masked in place.
+ * Assignment p in [0, 2^C): bit c of p is the recording of output c; y_n = sum of the outputs
+ * with bit n (an empty set gives 0).  EPS = 1e-8.
+ *   mode CTN_MIXIT_SNR:    snr_n = 10 log10((X_n + EPS) / (R_n + tau X_n + EPS)), X_n = sum x_n^2,
+ *                          R_n = sum (x_n - y_n)^2, tau = 10^(-snr_max / 10);
+ *   mode CTN_MIXIT_SI_SNR: the SI-SNR of ctn_pit_forward on (y_n, x_n), both with their own
+ *                          mean over t < length removed; snr_max is not read.
+ * max_snr[m] = max_p (snr_0 + snr_1) / 2, the first maximum in ascending p -> assign[m];
+ * loss = -mean_m max_snr[m]; remix [M][2][T] (nullable) = y_n under assign[m], added in fp32
+ * in ascending c, zero at t >= length.  All statistics and the search are fp64 in a fixed
+ * order without atomics: two calls on the same inputs give the same bits.  coef [M][2][4]
+ * (al, be, off, unused) is saved for the backward,
+ *   g_est[m][c][t] = (g_max_snr[m] - g_loss / M) (al_n x_n[t] + be_n y_n[t] + off_n), n = bit c
+ * of assign[m], for t < length and exactly 0 beyond (g_max_snr nullable: zeros).
+ * An unsupported descriptor (C < 2, C > 8, unknown mode, non-finite snr_max) has 0 workspace
+ * bytes; the entries check descriptor, pointers and workspace before anything is launched,
+ * and neither synchronises (both can be captured into a graph).
+ * ------------------------------------------------------------------------- */
+enum { CTN_MIXIT_SNR = 0, CTN_MIXIT_SI_SNR = 1 };
+typedef struct { int32_t M, C, T, mode; float snr_max; } ctn_mixit_desc;
+size_t ctn_mixit_workspace_bytes(const ctn_mixit_desc* d);
+int ctn_mixit_forward(const ctn_mixit_desc* d, const float* mixtures, const float* est, const int64_t* lengths,
+                      float* loss, float* max_snr /*[M]*/, int64_t* assign /*[M]*/, float* remix /*[M][2][T]*/,
+                      float* coef /*[M][2][4]*/, void* ws, size_t ws_bytes, void* stream);
+int ctn_mixit_backward(const ctn_mixit_desc* d, const float* mixtures, const float* est, const int64_t* lengths,
+                       const int64_t* assign, const float* coef, const float* g_loss, const float* g_max_snr,
+                       float* g_est /*[M][C][T]*/, void* stream);
+
+/* -------------------------------------------------------------------------
  * BSS Eval v3 source metrics (ABI v13): the energies behind the SDR / SIR / SAR of
  * mir_eval.separation.bss_eval_sources, which src/evaluate.py:90-105 calls on the host
  * once per utterance.  For M utterances, C references and E scored signals per utterance,
