@@ -67,13 +67,21 @@ def _norm_rows(norm_mod, rows, fr):
 
 class ConvTasNet(nn.Module):
     def __init__(self, N, L, B, H, P, X, R, C, norm_type="gLN", causal=False,
-                 mask_nonlinear='relu'):
-        """conv_tasnet.py:14-43 — same arguments, attributes, submodules and init."""
+                 mask_nonlinear='relu', mixture_consistency='none'):
+        """conv_tasnet.py:14-43 — same arguments, attributes, submodules and init.
+        mixture_consistency ('none', 'uniform' or 'power'; keyword beyond the reference's
+        signature): project the decoder output so that the C estimates add up to the input
+        mixture (mixture_consistency.py).  The layer has no parameters."""
         super(ConvTasNet, self).__init__()
         self.N, self.L, self.B, self.H, self.P, self.X, self.R, self.C = N, L, B, H, P, X, R, C
         self.norm_type = norm_type
         self.causal = causal
         self.mask_nonlinear = mask_nonlinear
+        if mixture_consistency not in ('none', 'uniform', 'power'):
+            raise ValueError(f"mixture_consistency {mixture_consistency!r}: one of 'none', 'uniform', 'power'")
+        if mixture_consistency != 'none' and not 2 <= C <= 16:
+            raise ValueError(f"mixture_consistency {mixture_consistency!r} needs 2 to 16 outputs, got C={C}")
+        self.mixture_consistency = mixture_consistency
         self.encoder = Encoder(L, N)
         self.separator = TemporalConvNet(N, B, H, P, X, R, C, norm_type, causal, mask_nonlinear)
         self.decoder = Decoder(N, L)
@@ -95,8 +103,10 @@ class ConvTasNet(nn.Module):
         # two per block); bit-identical gradients.
         self.defer_grad_reduce = True
 
-    def forward(self, mixture):
-        """mixture [M, T] -> est_source [M, C, T] (conv_tasnet.py:45-60)."""
+    def forward(self, mixture, lengths=None):
+        """mixture [M, T] -> est_source [M, C, T] (conv_tasnet.py:45-60).  lengths [M] (optional)
+        is read by the mixture-consistency projection only: samples at or past an utterance's
+        length are left as the decoder gave them."""
         L.require_device(mixture, "ConvTasNet")
         _mask_code(self.mask_nonlinear)
         norm = _norm_code(self.norm_type)
@@ -118,8 +128,13 @@ class ConvTasNet(nn.Module):
         defer = self.defer_grad_reduce and torch.is_grad_enabled() and norm != L.NORM_BN
         for blk, pk in zip(blocks, packs):
             x = blk._forward_rows(x, fr, norm, pk, split, defer)
-        return ops.DecoderFn.apply(x, w_rows, fr, (T, self.N, self.L, self.B, self.C, _mask_code(self.mask_nonlinear)),
-                                   sep.network[3].weight, self.decoder.basis_signals.weight)
+        est = ops.DecoderFn.apply(x, w_rows, fr, (T, self.N, self.L, self.B, self.C, _mask_code(self.mask_nonlinear)),
+                                  sep.network[3].weight, self.decoder.basis_signals.weight)
+        if self.mixture_consistency == 'none':
+            return est
+        if est.dtype != torch.float32 or not est.is_contiguous():
+            est = est.float().contiguous()
+        return ops.MixConFn.apply(mixture, est, lengths, self.mixture_consistency)[0]
 
     @classmethod
     def load_model(cls, path):
@@ -133,7 +148,8 @@ class ConvTasNet(nn.Module):
         model = cls(package['N'], package['L'], package['B'], package['H'],
                     package['P'], package['X'], package['R'], package['C'],
                     norm_type=package['norm_type'], causal=package['causal'],
-                    mask_nonlinear=package['mask_nonlinear'])
+                    mask_nonlinear=package['mask_nonlinear'],
+                    mixture_consistency=package.get('mixture_consistency', 'none'))
         model.load_state_dict(package['state_dict'])
         return model
 
@@ -149,6 +165,8 @@ class ConvTasNet(nn.Module):
             'optim_dict': optimizer.state_dict(),
             'epoch': epoch
         }
+        if getattr(model, 'mixture_consistency', 'none') != 'none':   # default packages keep the reference's keys
+            package['mixture_consistency'] = model.mixture_consistency
         if tr_loss is not None:
             package['tr_loss'] = tr_loss
             package['cv_loss'] = cv_loss

@@ -76,6 +76,14 @@ class MixitDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("M", "C", "T", "mode")] + [("snr_max", ctypes.c_float)]
 
 
+MIXCON_UNIFORM, MIXCON_POWER = 0, 1
+
+
+class MixconDesc(ctypes.Structure):
+    """ctn_mixcon_desc (include/ctn.h): mixture consistency; mode MIXCON_UNIFORM / MIXCON_POWER."""
+    _fields_ = [(n, c_int32) for n in ("M", "C", "T", "mode")]
+
+
 class BssDesc(ctypes.Structure):
     """ctn_bss_desc (include/ctn.h, ABI v13); T is the row stride in samples."""
     _fields_ = [(n, c_int32) for n in ("M", "C", "E", "T", "flen")]
@@ -190,6 +198,9 @@ _SIGS = {
     "ctn_mixit_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_mixit_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "ctn_mixit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p]),
+    "ctn_mixcon_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_mixcon_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_mixcon_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p, c_size_t, c_void_p]),
     "ctn_bss_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_bss_eval": (ctypes.c_int, [c_void_p] * 6 + [c_void_p, c_size_t, c_void_p]),
     "ctn_stoi_table_doubles": (c_size_t, [c_void_p]),

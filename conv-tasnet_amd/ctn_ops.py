@@ -728,6 +728,76 @@ class MixITFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
+# mixture-consistency projection (ctn_mixcon.hip; include/ctn.h ctn_mixcon_*)
+# ----------------------------------------------------------------------------
+MIXCON_MODES = {"uniform": L.MIXCON_UNIFORM, "power": L.MIXCON_POWER}
+
+
+def _mixcon_ws(lib, desc, dev):
+    nb = lib.ctn_mixcon_workspace_bytes(ctypes.byref(desc))
+    if nb == 0:
+        raise L.CtnLibraryError("mixture consistency: " + lib.ctn_last_error().decode(errors="replace"))
+    return L.workspace(nb, dev), nb
+
+
+class MixConFn(torch.autograd.Function):
+    """(mixture [M,T], est [M,C,T], lengths [M] or None, mode) -> (out [M,C,T], coef): the
+    outputs with the residual mixture - sum_c est_c spread over them at t < length.  mode:
+    "uniform" or "power"; coef [M,C+1] fp64 (weights and their denominator) in power mode,
+    else None.  Nothing is done in place."""
+
+    @staticmethod
+    def forward(ctx, mixture, est, lengths=None, mode="uniform"):
+        lib = L.load()
+        L.require_device(est, "mixture_consistency")
+        if mode not in MIXCON_MODES:
+            raise ValueError(f"mixture consistency {mode!r}: one of {sorted(MIXCON_MODES)}")
+        if est.dim() != 3 or mixture.dim() != 2 or tuple(mixture.shape) != (est.size(0), est.size(2)):
+            raise ValueError(f"mixture consistency: mixture {tuple(mixture.shape)} must be [M, T] for estimates "
+                             f"{tuple(est.shape)} [M, C, T]")
+        if est.dtype != torch.float32 or not est.is_contiguous():
+            raise L.CtnLibraryError("est must be a contiguous float32 tensor")
+        dev = est.device
+        mixture = _f32(mixture.to(dev))
+        M, C, T = est.shape
+        if lengths is not None:
+            lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+            if lengths.numel() != M:
+                raise ValueError(f"mixture consistency: {lengths.numel()} lengths for {M} utterances")
+        desc = L.MixconDesc(M, C, T, MIXCON_MODES[mode])
+        ws, nb = _mixcon_ws(lib, desc, dev)
+        out = torch.empty_like(est)
+        coef = torch.empty(M, C + 1, dtype=torch.float64, device=dev) if mode == "power" else None
+        L.check(lib.ctn_mixcon_forward(ctypes.byref(desc), mixture.data_ptr(), est.data_ptr(), L.ptr(lengths),
+                                       out.data_ptr(), L.ptr(coef), ws.data_ptr(), nb, L.stream_handle(dev)),
+                "ctn_mixcon_forward")
+        ctx.desc = (M, C, T, MIXCON_MODES[mode])
+        ctx.has_len, ctx.has_coef = lengths is not None, coef is not None
+        ctx.save_for_backward(mixture, est, *([lengths] if ctx.has_len else []), *([coef] if ctx.has_coef else []))
+        if coef is not None:
+            ctx.mark_non_differentiable(coef)
+        return out, coef
+
+    @staticmethod
+    def backward(ctx, g_out, _g_coef):
+        lib = L.load()
+        saved = list(ctx.saved_tensors)
+        mixture, est = saved[0], saved[1]
+        lengths = saved[2] if ctx.has_len else None
+        coef = saved[-1] if ctx.has_coef else None
+        desc = L.MixconDesc(*ctx.desc)
+        dev = est.device
+        g_out = _f32(g_out)
+        g_est = torch.empty_like(est)
+        g_mix = torch.empty_like(mixture) if ctx.needs_input_grad[0] else None
+        ws, nb = _mixcon_ws(lib, desc, dev)
+        L.check(lib.ctn_mixcon_backward(ctypes.byref(desc), mixture.data_ptr(), est.data_ptr(), L.ptr(lengths),
+                                        L.ptr(coef), g_out.data_ptr(), g_est.data_ptr(), L.ptr(g_mix),
+                                        ws.data_ptr(), nb, L.stream_handle(dev)), "ctn_mixcon_backward")
+        return g_mix, g_est, None, None
+
+
+# ----------------------------------------------------------------------------
 # stand-alone separator layers on frame rows (ctn_layers.hip; include/ctn.h ABI v4):
 # the module forwards of TemporalConvNet / DepthwiseSeparableConv / gLN / cLN when
 # they are called on their own (conv_tasnet.py:192-209, 265-272, 319-329, 344-355)

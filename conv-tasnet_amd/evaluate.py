@@ -116,6 +116,8 @@ class Evaluator:
         """[B, T] -> [B, C, T]: the whole-signal forward, or with --chunk_s each utterance
         windowed at its own length (zeros past it, as the padded forward's tail is ignored)."""
         if self.chunker is None:
+            if getattr(self.model, 'mixture_consistency', 'none') != 'none':   # from the package
+                return self.model(mixture, lengths)
             return self.model(mixture)
         from separate import chunked_estimates
         ests = chunked_estimates(self.chunker, mixture, lengths)

@@ -292,9 +292,18 @@ class ChunkedSeparator:
     def windows(self, mixture: torch.Tensor) -> torch.Tensor:
         return frame(mixture, self.window, self.overlap)
 
-    def forward_windows(self, win: torch.Tensor) -> torch.Tensor:
-        """[J, W] -> P [J, C, W] fp32, one forward per ``batch`` windows."""
-        parts = [self.model(win[b:b + self.batch]) for b in range(0, win.shape[0], self.batch)]
+    def forward_windows(self, win: torch.Tensor, T: int | None = None) -> torch.Tensor:
+        """[J, W] -> P [J, C, W] fp32, one forward per ``batch`` windows.  A ConvTasNet with
+        mixture consistency on also gets each window's valid length (T: the recording's
+        samples; only the zero-padded last window is shorter than W), so that the padding is
+        not projected; any other callable is called as before."""
+        if T is not None and getattr(self.model, "mixture_consistency", "none") != "none":
+            Hs = self.window - self.overlap
+            valid = (T - Hs * torch.arange(win.shape[0], device=win.device)).clamp(0, self.window)
+            parts = [self.model(win[b:b + self.batch], valid[b:b + self.batch])
+                     for b in range(0, win.shape[0], self.batch)]
+        else:
+            parts = [self.model(win[b:b + self.batch]) for b in range(0, win.shape[0], self.batch)]
         for p in parts:
             if p.dim() != 3 or p.shape[-1] != self.window:
                 raise ValueError(f"model output of shape {tuple(p.shape)}: expected [B, C, {self.window}]")
@@ -309,7 +318,7 @@ class ChunkedSeparator:
         if mixture.dim() != 1 or mixture.numel() < 1:
             raise ValueError(f"mixture of shape {tuple(mixture.shape)}: expected [T] or [1, T]")
         T = mixture.numel()
-        P = self.forward_windows(self.windows(mixture))
+        P = self.forward_windows(self.windows(mixture), T)
         res = stitch(P, T, self.overlap, self.fade)
         self.perm, self.sigma, self.status, self.sim = res.perm, res.sigma, res.status, res.sim
         return res.out

@@ -74,7 +74,10 @@ class Separator:
         if self.chunker is not None:
             return remove_pad(mixture, lengths), [e.cpu().numpy() for e in chunked_estimates(self.chunker, mixture,
                                                                                                lengths)]
-        est = self.model(mixture)
+        if getattr(self.model, 'mixture_consistency', 'none') != 'none':   # from the package
+            est = self.model(mixture, lengths)
+        else:
+            est = self.model(mixture)
         return remove_pad(mixture, lengths), remove_pad(est, lengths)
 
     def save(self, out_dir: str, name: str, mixture, estimates):

@@ -202,8 +202,10 @@ class Solver(object):
 
     def _loss(self, model, mixture, lengths, source, cross_valid):
         """The loss of one batch: PIT against the sources, or, with --loss mixit, MixIT."""
+        # with mixture consistency on (DESIGN.md §28) the model projects within each length
+        mc = getattr(_inner(model), 'mixture_consistency', 'none') != 'none'
         if not self.mixit:
-            return cal_loss(source, model(mixture), lengths)[0]
+            return cal_loss(source, model(mixture, lengths) if mc else model(mixture), lengths)[0]
         from mixit_criterion import cal_mixit_loss, mom_pairs
         if cross_valid:
             # remix evaluation: the model's outputs remixed to the two true sources
@@ -213,7 +215,8 @@ class Solver(object):
         else:
             # utterances 2m and 2m+1 become one mixture of mixtures; the sources are not used
             mixture, refs, lens = mom_pairs(mixture, lengths)
-        return cal_mixit_loss(refs, model(mixture), lens, self.mixit_loss, self.mixit_snr_max)[0]
+        est = model(mixture, lens) if mc else model(mixture)
+        return cal_mixit_loss(refs, est, lens, self.mixit_loss, self.mixit_snr_max)[0]
 
     def _run_one_epoch(self, epoch, cross_valid=False):
         """One pass over the train (or cv) loader -> mean loss over all ranks (solver.py:158-210)."""

@@ -72,6 +72,13 @@ class StreamingSeparator:
             raise ValueError("the encoder stride L//2 must tile the frame (even L)")
         if act_dtype not in (None, torch.float32):
             raise ValueError("streaming computes in fp32")
+        mc = getattr(model, "mixture_consistency", "none")
+        if mc == "power":
+            raise ValueError("mixture consistency 'power' weighs the outputs by their energy over the whole "
+                             "utterance (like gLN): such a model cannot stream")
+        if mc != "none":
+            raise ValueError(f"mixture consistency {mc!r} needs the input samples aligned with the delayed "
+                             f"output, which the streamer does not keep: such a model cannot stream")
         self.model = model
         self.norm = norm
         self.stride = model.L // 2

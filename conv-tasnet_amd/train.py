@@ -32,7 +32,10 @@ Differences, each deliberate:
   the MixIT loss (``--mixit_loss snr|si_snr``, ``--mixit_snr_max``) scores the best remix
   against the two mixtures; ``--batch_size`` must be even.  With ``--dynamic_mix 1`` the mixer
   draws ``--mixit_speakers`` speakers per single mixture.  Cross validation remixes the
-  outputs to the two sources of each validation mixture.
+  outputs to the two sources of each validation mixture;
+* ``--mixture_consistency uniform|power`` (default ``none``: nothing changes) puts the
+  mixture-consistency projection on the model's outputs (mixture_consistency.py, DESIGN.md
+  §28), with either loss; the mode is written into the package.
 """
 import argparse
 import os
@@ -171,6 +174,21 @@ parser.add_argument('--mixit_speakers', default=2, type=int,
                     help='Speakers the dynamic mixer draws per single mixture under --loss mixit')
 
 
+# mixture consistency (mixture_consistency.py); none: the reference's model
+parser.add_argument('--mixture_consistency', default='none', type=str, choices=['none', 'uniform', 'power'],
+                    help='Project the model outputs so that they add up to the input mixture: the residual is '
+                         'spread evenly (uniform) or by output power (power); works with either --loss')
+
+
+def check_mixture_consistency(args):
+    """--mixture_consistency uniform|power needs 2 to 16 model outputs."""
+    mode = getattr(args, 'mixture_consistency', 'none')
+    if mode not in ('none', 'uniform', 'power'):
+        raise ValueError(f"--mixture_consistency {mode}: one of none, uniform, power")
+    if mode != 'none' and not 2 <= args.C <= 16:
+        raise ValueError(f"--mixture_consistency {mode}: --C {args.C} must be 2 to 16")
+
+
 def check_mixit(args):
     """--loss mixit pairs the utterances of a batch and needs at least two model outputs."""
     import math
@@ -278,6 +296,7 @@ class FlatDP(Single):
 
 def main(args):
     check_mixit(args)
+    check_mixture_consistency(args)
     check_dm_speeds(args)
     check_dm_aug(args)
     if args.dynamic_mix and not args.use_cuda:
@@ -309,7 +328,7 @@ def main(args):
     # model
     model = ConvTasNet(args.N, args.L, args.B, args.H, args.P, args.X, args.R,
                        args.C, norm_type=args.norm_type, causal=args.causal,
-                       mask_nonlinear=args.mask_nonlinear)
+                       mask_nonlinear=args.mask_nonlinear, mixture_consistency=getattr(args, 'mixture_consistency', 'none'))
     if args.bf16:
         model.act_dtype = torch.bfloat16
     if rank == 0:

@@ -263,6 +263,42 @@ int ctn_mixit_backward(const ctn_mixit_desc* d, const float* mixtures, const flo
                        float* g_est /*[M][C][T]*/, void* stream);
 
 /* -------------------------------------------------------------------------
+ * Mixture-consistency projection (Wisdom et al. 2019, "Differentiable consistency
+ * constraints for improved deep speech enhancement"): the residual of the model's C outputs
+ * against the input mixture is spread over the outputs, so that they add up to the mixture.
+ * Added within ABI v13 without a version bump (nothing existing changed): callers probe for
+ * the symbol.  No reference counterpart; DESIGN.md §28 has the full definition.
+ *
+ * mixture [M][T], est [M][C][T] fp32 contiguous, 2 <= C <= 16, lengths [M] int64 or null
+ * (= T); n = min(max(lengths[m], 0), T).  EPS = 1e-8.  For t < n
+ *   r[t] = x[t] - sum_j s_j[t] (ascending j),  out_c[t] = s_c[t] + w_c r[t],
+ * evaluated in fp64 per sample and rounded to fp32 once; for t >= n out_c[t] = s_c[t] bit for
+ * bit.  Not in place (out != est).
+ *   mode CTN_MIXCON_UNIFORM: w_c = 1 / C; coef is not touched (nullable).
+ *   mode CTN_MIXCON_POWER:   p_c = sum_{t<n} s_c[t]^2, D = sum_c p_c + C EPS,
+ *                            w_c = (p_c + EPS) / D; coef [M][C+1] fp64 receives w_c and D and
+ *                            is what the backward reads.
+ * Backward, g_out = dL/d out:  G[t] = sum_c w_c g_c[t],
+ *   g_est_k[t] = g_k[t] - G[t] + 2 s_k[t] (a_k - sum_c w_c a_c) / D,  a_c = sum_{t<n} g_c[t] r[t]
+ * (the third term in power mode only), g_mixture[t] = G[t] (nullable: not written); for
+ * t >= n g_est = g_out bit for bit and g_mixture = 0.  fp64 per sample, rounded once.  In
+ * uniform mode the backward reads neither mixture, est nor coef (all nullable).
+ * All sums are fp64 in a fixed order without atomics: two calls on the same inputs give the
+ * same bits.  One workspace size serves both directions.  An unsupported descriptor
+ * (C < 2, C > 16, M or T < 1, unknown mode) has 0 workspace bytes; the entries check
+ * descriptor, pointers and workspace before anything is launched, and neither synchronises
+ * (both can be captured into a graph).
+ * ------------------------------------------------------------------------- */
+enum { CTN_MIXCON_UNIFORM = 0, CTN_MIXCON_POWER = 1 };
+typedef struct { int32_t M, C, T, mode; } ctn_mixcon_desc;
+size_t ctn_mixcon_workspace_bytes(const ctn_mixcon_desc* d);
+int ctn_mixcon_forward(const ctn_mixcon_desc* d, const float* mixture, const float* est, const int64_t* lengths,
+                       float* out /*[M][C][T]*/, double* coef /*[M][C+1]*/, void* ws, size_t ws_bytes, void* stream);
+int ctn_mixcon_backward(const ctn_mixcon_desc* d, const float* mixture, const float* est, const int64_t* lengths,
+                        const double* coef, const float* g_out, float* g_est /*[M][C][T]*/,
+                        float* g_mixture /*[M][T]*/, void* ws, size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------------------------
  * BSS Eval v3 source metrics (ABI v13): the energies behind the SDR / SIR / SAR of
  * mir_eval.separation.bss_eval_sources, which src/evaluate.py:90-105 calls on the host
  * once per utterance.  For M utterances, C references and E scored signals per utterance,
