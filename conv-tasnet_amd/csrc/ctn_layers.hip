@@ -136,6 +136,11 @@ __global__ __launch_bounds__(LY_NT) void ln_dx_kernel(const T* x, const T* gy, i
     const int c = (int)(i - row * C);
     float o = 0.f;
     if (row % g.Kp < g.K) {
+      // No fma contraction here: g gamma is rounded to fp32 on its own, as the terms of its
+      // group mean were.  Fused with - sm.x the product keeps its rounding residual
+      // (2^-24 |g gamma|), which a constant row's rstd = 1/sqrt(eps) = 1e4 multiplies
+      // (cLN at C = 1: gx is exactly 0, and came out at 6e-4 |g gamma|).
+#pragma clang fp contract(off)
       const long gi = NK == NORM_GLN ? row / g.Kp : row;
       const float2 st = stats[gi], sm = sums[gi];
       const float xh = (Io<T>::ld(x + i) - st.x) * st.y;

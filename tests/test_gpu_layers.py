@@ -3,7 +3,11 @@ GlobalLayerNorm / ChannelwiseLayerNorm against the reference's own golden vector
 (tests/golden/ops.npz, captured from src/conv_tasnet.py:307-355), and
 DepthwiseSeparableConv / TemporalConvNet against the fp32 CPU oracle (oracle/, test
 infrastructure), forward and backward.  Tolerances: fp32 outputs 1e-5 relative L2,
-gradients 1e-4 (1e-3 for the cancelling PReLU alpha sums); bf16 5e-2.  GPU only."""
+gradients 1e-4 (1e-3 for the cancelling PReLU alpha sums); bf16 5e-2.  GPU only.
+
+One geometry per module and whole-tensor norms: the edges (row-block, pad, finalize and
+slab_reduce switches, poisoned padding, bf16 backward, the mask kernels on their own) are
+held element by element against an fp64 oracle in tests/test_gpu_layers_alone.py."""
 import os
 
 import numpy as np
