@@ -157,7 +157,7 @@ extern "C" int ctn_stream_call(const ctn_stream_desc* d, const ctn_stream_model*
   if (pos < 0) return fail(CTN_ERR_ARG, "pos %lld", (long long)pos);
   if (tail_in == tail_out) return fail(CTN_ERR_ARG, "tail_out must not alias tail_in");
   if (ld_samples < (int64_t)(d->K - 1) * (d->L / 2) + d->L) return fail(CTN_ERR_ARG, "ld_samples too small");
-  if (ws_bytes < ctn_stream_workspace_bytes(d)) return fail(CTN_ERR_ARG, "workspace too small");
+  if (ws_bytes < ctn_stream_workspace_bytes(d)) return fail(CTN_ERR_WORKSPACE, "workspace too small");
   for (int i = 0; i < mdl->nblocks; ++i) {
     const ctn_stream_block_params& b = mdl->blocks[i];
     if (b.dilation < 1 || b.ring_frames < 1 || (b.ring_frames & (b.ring_frames - 1)) ||
@@ -219,6 +219,10 @@ extern "C" int ctn_stream_call(const ctn_stream_desc* d, const ctn_stream_model*
                         (const void*)tail_out, (const void*)out, (const void*)ws})
     key.push_back((uintptr_t)v);
   key.push_back((uintptr_t)ld_samples);
+  {   // a forced chunk width (ctn_stream.hip, sc_width) picks other kernels: another graph
+    const char* e = getenv("CTN_SC_W");
+    key.push_back((uintptr_t)(e ? (atoi(e) == 8 ? 8 : 32) : 0));
+  }
   for (int i = 0; i < mdl->nblocks; ++i) {
     const ctn_stream_block_params& b = mdl->blocks[i];
     key.push_back((uintptr_t)(unsigned)b.dilation);
