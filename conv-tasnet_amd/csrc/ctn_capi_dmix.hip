@@ -60,6 +60,22 @@ extern "C" int ctn_dmix_draw(const ctn_dmix_desc* d, const int64_t* off, const i
   return CTN_OK;
 }
 
+extern "C" int ctn_dmix_thin(const ctn_dmix_desc* d, int32_t min_speakers, int64_t first_sample,
+                             const int64_t* first_sample_dev, int64_t drawn_advance, ctn_dmix_entry* plan,
+                             int32_t* count, void* stream) {
+  if (int rc = dmix_check(d)) return rc;
+  if (min_speakers < 1 || min_speakers > d->C)
+    return fail(CTN_ERR_ARG, "min_speakers=%d outside 1..C=%d", min_speakers, d->C);
+  if (!plan || !count) return fail(CTN_ERR_ARG, "null pointer");
+  DmixThinArgs a{};
+  a.M = d->M; a.C = d->C; a.min_speakers = min_speakers;
+  a.seed_lo = (uint32_t)d->seed; a.seed_hi = (uint32_t)(d->seed >> 32);
+  a.first = first_sample; a.first_dev = first_sample_dev; a.back = drawn_advance;
+  a.plan = reinterpret_cast<DmixEntry*>(plan); a.count = count;
+  CTN_HIP(launch_dmix_thin(a, (hipStream_t)stream));
+  return CTN_OK;
+}
+
 extern "C" int ctn_dmix_mix(const ctn_dmix_desc* d, const void* pool, const int64_t* off, const ctn_dmix_entry* plan,
                             float* gains, float* sources, float* mixture, int32_t* status, void* ws, size_t ws_bytes,
                             void* stream) {

@@ -43,6 +43,18 @@ struct DmixDrawArgs {
   int64_t span[DMIX_MAX_SPEEDS];   // with `speed`: input samples a segment of speed k needs
 };
 
+constexpr uint32_t DMIX_COUNT_SLOT = 48;   // Philox counter word 2 of the speaker-count draw
+
+struct DmixThinArgs {
+  int M, C, min_speakers;
+  uint32_t seed_lo, seed_hi;
+  int64_t first;              // global sample of row 0 when first_dev is null
+  const int64_t* first_dev;   // the draw's counter, already advanced by `back`
+  int64_t back;
+  DmixEntry* plan;            // [M][C]
+  int32_t* count;             // [M]
+};
+
 struct DmixMixArgs {
   int M, C, T, U, pool_dtype, level_mode;
   float peak;
@@ -101,6 +113,7 @@ struct DmixResampleArgs {
 DmixLayout dmix_layout(int M, int C, int T);
 DmixSpLayout dmix_sp_layout(int M, int C, int T);
 hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s);
+hipError_t launch_dmix_thin(const DmixThinArgs& a, hipStream_t s);
 hipError_t launch_dmix_mix(const DmixMixArgs& a, hipStream_t s);
 // a.plan, a.off, a.pool, a.U, a.pool_dtype of `mix` are replaced by the resampled pool's.
 hipError_t launch_dmix_mix_sp(const DmixResampleArgs& r, DmixMixArgs mix, hipStream_t s);

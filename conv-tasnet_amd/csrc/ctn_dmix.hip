@@ -95,6 +95,26 @@ hipError_t launch_dmix_draw(const DmixDrawArgs& a, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------
+// thin: how many of a row's slots speak (ctn_dmix_thin)
+// ---------------------------------------------------------------------------
+// One thread per row: n_m = min + ((r0 (C - min + 1)) >> 32) from the row's own Philox draw;
+// slots c >= n_m get level_db = -inf, which the gain stage turns into a gain of exactly 0.
+__global__ __launch_bounds__(64) void dmix_thin_kernel(DmixThinArgs a) {
+  const int m = blockIdx.x * 64 + threadIdx.x;
+  if (m >= a.M) return;
+  const uint64_t g = (uint64_t)((a.first_dev ? *a.first_dev - a.back : a.first) + m);
+  const Philox r = philox4x32_10((uint32_t)g, (uint32_t)(g >> 32), DMIX_COUNT_SLOT, 0u, a.seed_lo, a.seed_hi);
+  const int n = a.min_speakers + (int)(((uint64_t)r.r[0] * (uint64_t)(a.C - a.min_speakers + 1)) >> 32);
+  for (int c = n; c < a.C; ++c) a.plan[(size_t)m * a.C + c].level_db = -INFINITY;
+  a.count[m] = n;
+}
+
+hipError_t launch_dmix_thin(const DmixThinArgs& a, hipStream_t s) {
+  dmix_thin_kernel<<<dim3((a.M + 63) / 64), dim3(64), 0, s>>>(a);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // mix
 // ---------------------------------------------------------------------------
 // grid: (m*C + c) * nchunk + chunk

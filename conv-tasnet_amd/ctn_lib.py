@@ -76,6 +76,15 @@ class MixitDesc(ctypes.Structure):
     _fields_ = [(n, c_int32) for n in ("M", "C", "T", "mode")] + [("snr_max", ctypes.c_float)]
 
 
+PITVAR_SNR, PITVAR_SI_SNR = 0, 1
+
+
+class PitVarDesc(ctypes.Structure):
+    """ctn_pitvar_desc (include/ctn.h): PIT with silent sources; mode PITVAR_SNR / PITVAR_SI_SNR."""
+    _fields_ = [(n, c_int32) for n in ("M", "C", "T", "mode")] + [("snr_max", ctypes.c_float),
+                                                                 ("inactive_snr_max", ctypes.c_float)]
+
+
 MIXCON_UNIFORM, MIXCON_POWER = 0, 1
 
 
@@ -198,6 +207,9 @@ _SIGS = {
     "ctn_mixit_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_mixit_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
     "ctn_mixit_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 8 + [c_void_p]),
+    "ctn_pitvar_workspace_bytes": (c_size_t, [c_void_p]),
+    "ctn_pitvar_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 9 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_pitvar_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p]),
     "ctn_mixcon_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_mixcon_forward": (ctypes.c_int, [c_void_p] + [c_void_p] * 5 + [c_void_p, c_size_t, c_void_p]),
     "ctn_mixcon_backward": (ctypes.c_int, [c_void_p] + [c_void_p] * 7 + [c_void_p, c_size_t, c_void_p]),
@@ -209,6 +221,8 @@ _SIGS = {
     "ctn_dmix_workspace_bytes": (c_size_t, [c_void_p]),
     "ctn_dmix_draw": (ctypes.c_int, [c_void_p] * 4 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p]),
     "ctn_dmix_mix": (ctypes.c_int, [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
+    "ctn_dmix_thin": (ctypes.c_int, [c_void_p, c_int32, ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p,
+                                     c_void_p]),
     "ctn_dmix_sp_filter_floats": (c_size_t, [c_void_p]),
     "ctn_dmix_sp_workspace_bytes": (c_size_t, [c_void_p, c_void_p]),
     "ctn_dmix_draw_sp": (ctypes.c_int, [c_void_p] * 5 + [ctypes.c_int64, c_void_p, ctypes.c_int64, c_void_p, c_void_p,

@@ -728,6 +728,74 @@ class MixITFn(torch.autograd.Function):
 
 
 # ----------------------------------------------------------------------------
+# PIT with silent sources (ctn_pitvar.hip; include/ctn.h ctn_pitvar_*)
+# ----------------------------------------------------------------------------
+PITVAR_MODES = {"snr": L.PITVAR_SNR, "si_snr": L.PITVAR_SI_SNR}
+
+
+class PITVarFn(torch.autograd.Function):
+    """(source [M,C,T], est [M,C,T], lengths, mixture [M,T] or None, mode, snr_max,
+    inactive_snr_max) -> (loss, max_snr [M,1], perm [M,C] int64, active [M,C] bool); nothing is
+    masked in place.  mode: "snr" or "si_snr"."""
+
+    @staticmethod
+    def forward(ctx, source, est, lengths, mixture=None, mode="snr", snr_max=30.0, inactive_snr_max=20.0):
+        lib = L.load()
+        L.require_device(est, "cal_loss_var")
+        if mode not in PITVAR_MODES:
+            raise ValueError(f"PIT-var loss {mode!r}: one of {sorted(PITVAR_MODES)}")
+        if est.dim() != 3 or tuple(source.shape) != tuple(est.shape):
+            raise ValueError(f"PIT-var: source {tuple(source.shape)} must match the estimates "
+                             f"{tuple(est.shape)} [M, C, T]")
+        if mixture is not None and tuple(mixture.shape) != (est.size(0), est.size(2)):
+            raise ValueError(f"PIT-var: mixture {tuple(mixture.shape)} must be [M, T] for estimates "
+                             f"{tuple(est.shape)} [M, C, T]")
+        if est.dtype != torch.float32 or not est.is_contiguous():
+            raise L.CtnLibraryError("estimate_source must be a contiguous float32 tensor")
+        dev = est.device
+        source = _f32(source.to(dev))
+        mixture = None if mixture is None else _f32(mixture.to(dev))
+        lengths = lengths.to(device=dev, dtype=torch.int64).contiguous()
+        M, C, T = est.shape
+        if lengths.numel() != M:
+            raise ValueError(f"PIT-var: {lengths.numel()} lengths for {M} utterances")
+        desc = L.PitVarDesc(M, C, T, PITVAR_MODES[mode], float(snr_max), float(inactive_snr_max))
+        nb = lib.ctn_pitvar_workspace_bytes(ctypes.byref(desc))
+        if nb == 0:
+            raise L.CtnLibraryError("PIT-var: " + lib.ctn_last_error().decode(errors="replace"))
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        max_snr = torch.empty(M, 1, dtype=torch.float32, device=dev)
+        perm = torch.empty(M, C, dtype=torch.int64, device=dev)
+        active = torch.empty(M, C, dtype=torch.bool, device=dev)
+        coef = torch.empty(M, C, 4, dtype=torch.float32, device=dev)
+        ws = L.workspace(nb, dev)
+        L.check(lib.ctn_pitvar_forward(ctypes.byref(desc), source.data_ptr(), est.data_ptr(), L.ptr(mixture),
+                                       lengths.data_ptr(), loss.data_ptr(), max_snr.data_ptr(), perm.data_ptr(),
+                                       active.data_ptr(), coef.data_ptr(), ws.data_ptr(), nb, L.stream_handle(dev)),
+                "ctn_pitvar_forward")
+        ctx.mark_non_differentiable(perm, active)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(source, est, lengths, coef)
+        ctx.desc = (M, C, T, PITVAR_MODES[mode], float(snr_max), float(inactive_snr_max))
+        return loss, max_snr, perm, active
+
+    @staticmethod
+    def backward(ctx, g_loss, g_max_snr, _g_perm, _g_active):
+        lib = L.load()
+        source, est, lengths, coef = ctx.saved_tensors
+        M = ctx.desc[0]
+        desc = L.PitVarDesc(*ctx.desc)
+        dev = est.device
+        g_est = torch.empty_like(est)
+        gl = _f32(g_loss.reshape(1)) if g_loss is not None else torch.zeros(1, device=dev)
+        gm = _f32(g_max_snr.reshape(M)) if g_max_snr is not None else None
+        L.check(lib.ctn_pitvar_backward(ctypes.byref(desc), source.data_ptr(), est.data_ptr(), lengths.data_ptr(),
+                                        coef.data_ptr(), gl.data_ptr(), L.ptr(gm), g_est.data_ptr(),
+                                        L.stream_handle(dev)), "ctn_pitvar_backward")
+        return None, g_est, None, None, None, None, None
+
+
+# ----------------------------------------------------------------------------
 # mixture-consistency projection (ctn_mixcon.hip; include/ctn.h ctn_mixcon_*)
 # ----------------------------------------------------------------------------
 MIXCON_MODES = {"uniform": L.MIXCON_UNIFORM, "power": L.MIXCON_POWER}

@@ -228,6 +228,27 @@ MAX_RIR_TAPS = 16384
 _RIR_SLOT, _NOISE_SLOT = 16, 32                          # Philox counter word 2 of the RIR and noise draws
 
 
+_COUNT_SLOT = 48                                         # Philox counter word 2 of the speaker-count draw
+
+
+def thin_host(plan, M, C, seed, first_sample, min_speakers):
+    """ctn_dmix_thin on the host -> (plan, count [M] int32): a copy of `plan` in which row m keeps
+    its first n_m = min_speakers + ((r0 (C - min_speakers + 1)) >> 32) slots and the others have
+    level_db = -inf (a gain of exactly 0 in mix_host / mix_aug_host); r0 is word 0 of the row's
+    own draw at counter word 2 = 48, so the count depends on (seed, global sample) alone."""
+    if not 1 <= int(min_speakers) <= C:
+        raise ValueError(f"min_speakers={min_speakers} outside 1..C={C}")
+    plan = np.array(plan, dtype=PLAN_DTYPE, copy=True).reshape(M, C)
+    key = (int(seed) & _U32, (int(seed) >> 32) & _U32)
+    count = np.zeros(M, np.int32)
+    for m in range(M):
+        g = (int(first_sample) + m) & 0xFFFFFFFFFFFFFFFF
+        r = philox4x32_10((g & _U32, g >> 32, _COUNT_SLOT, 0), key)
+        count[m] = int(min_speakers) + ((r[0] * (C - int(min_speakers) + 1)) >> 32)
+        plan["level_db"][m, count[m]:] = -np.inf
+    return plan, count
+
+
 def reverb_host(xs, h):
     """The reverberated segment of ctn_dmix_mix_aug: xv[n] = sum_{j <= min(n, L - 1)} h[j] xs[n - j],
     j upward, acc = fl32(acc + fl32(h[j] xs[n - j])) from +0; the segment starts from silence."""
@@ -501,10 +522,15 @@ class DynamicMixer:
     rirs: a RirBank: every slot is convolved with one of its responses with probability rir_prob
     (`.rir` holds the drawn indices, -1: dry).  noise: a DeviceCorpus: every row gets one of its
     segments at an SNR drawn from snr_db = (lo, hi) (`.nplan`, `.ngain`).  Either one selects
-    ctn_dmix_draw_aug / ctn_dmix_mix_aug; both None: the entry points above."""
+    ctn_dmix_draw_aug / ctn_dmix_mix_aug; both None: the entry points above.
+    min_speakers: 1 <= K < C: every row keeps a drawn number n_m in [K, C] of its slots
+    (ctn_dmix_thin after the draw; `.count` holds n_m) and the others are silent: their
+    level_db is -inf, their gain and every sample of their source exactly 0.  None or C: every
+    slot speaks and no further kernel runs."""
 
     def __init__(self, corpus, M, C, T, seed=0, level_mode=0, level_db=(-2.5, 2.5), peak=0.9, max_tries=16,
-                 rank=0, world=1, speeds=None, rirs=None, rir_prob=1.0, noise=None, snr_db=(-5.0, 5.0)):
+                 rank=0, world=1, speeds=None, rirs=None, rir_prob=1.0, noise=None, snr_db=(-5.0, 5.0),
+                 min_speakers=None):
         import torch
 
         import ctn_lib as L
@@ -513,6 +539,9 @@ class DynamicMixer:
         L.require_device(corpus.pool, "DynamicMixer")
         self.corpus, self.M, self.C, self.T = corpus, int(M), int(C), int(T)
         self.rank, self.world = int(rank), int(world)
+        if min_speakers is not None and not 1 <= int(min_speakers) <= self.C:
+            raise ValueError(f"min_speakers={min_speakers} outside 1..C={self.C}")
+        self.min_speakers = None if min_speakers is None or int(min_speakers) == self.C else int(min_speakers)
         ratios = None if speeds is None else _speed_table(speeds)
         if ratios is not None and all(r == (1, 1) for r in ratios):
             ratios = None
@@ -567,6 +596,7 @@ class DynamicMixer:
         self.gains = torch.zeros(self.M, self.C, dtype=torch.float32, device=dev)
         self.status = torch.zeros(self.M, dtype=torch.int32, device=dev)
         self.lengths = torch.full((self.M,), self.T, dtype=torch.int64, device=dev)
+        self.count = torch.full((self.M,), self.C, dtype=torch.int32, device=dev)
         if ratios is not None:
             taps = np.concatenate([speed_filter(up, down)[0] for up, down in ratios if (up, down) != (1, 1)])
             if len(taps) != self._lib.ctn_dmix_sp_filter_floats(ctypes.byref(self._sp)):
@@ -596,7 +626,17 @@ class DynamicMixer:
 
     def draw(self, first_sample=0, counter=None, advance=0):
         """Fill self.plan for the rows first_sample + m, or *counter + m (a device int64
-        tensor of one element, to which `advance` is then added on the device)."""
+        tensor of one element, to which `advance` is then added on the device).  With
+        min_speakers the plan is then thinned and self.count filled."""
+        import ctn_lib as L
+        self._draw(first_sample, counter, advance)
+        if self.min_speakers is not None:
+            L.check(self._lib.ctn_dmix_thin(ctypes.byref(self.desc), self.min_speakers, int(first_sample),
+                                            L.ptr(counter), int(advance), L.ptr(self.plan), L.ptr(self.count),
+                                            L.stream_handle(self.corpus.device)), "ctn_dmix_thin")
+        return self.plan
+
+    def _draw(self, first_sample, counter, advance):
         import torch
 
         import ctn_lib as L

@@ -30,7 +30,13 @@ Same flags and printout as the reference.  Differences, each deliberate:
 * ``--mixit_remix 1`` (default 0: nothing changes) scores a MixIT-trained model, which has
   more outputs than the mixture has sources: its outputs are remixed to the two sources by
   the best assignment (``mixit_criterion.cal_mixit_loss``, csrc/ctn_mixit.hip)
-  and the remixed pair takes the place of the PIT-paired estimates in every metric.
+  and the remixed pair takes the place of the PIT-paired estimates in every metric;
+* ``--var_speakers 1`` (default 0: nothing changes) scores a model trained with ``--loss pit_var``
+  on mixtures whose silent sources are all-zero files: outputs and sources are paired by
+  ``pit_var_criterion.cal_loss_var`` (csrc/ctn_pitvar.hip), SI-SNRi is averaged
+  over the active sources only, and ``var_records`` keeps, per utterance, the mean level of the
+  outputs paired with silent sources (dB relative to the mixture) and whether the number of
+  outputs above ``--var_count_db`` equals the number of active sources.
 """
 import argparse
 
@@ -74,6 +80,17 @@ parser.add_argument('--mixit_loss', default='snr', type=str, choices=['snr', 'si
                     help='Score that picks the assignment of --mixit_remix 1')
 parser.add_argument('--mixit_snr_max', default=30.0, type=float,
                     help='Soft SNR ceiling in dB of --mixit_loss snr')
+parser.add_argument('--var_speakers', default=0, type=int,
+                    help='1: the mixtures hold 1 to C speakers (silent sources are all-zero files): pair by the '
+                         'pit_var loss, average SI-SNRi over the active sources, report the silent outputs')
+parser.add_argument('--var_count_db', default=-20.0, type=float,
+                    help='--var_speakers 1: an output above this level (dB relative to the mixture) counts as a speaker')
+parser.add_argument('--var_loss', default='snr', type=str, choices=['snr', 'si_snr'],
+                    help='Score of an active source that picks the pairing of --var_speakers 1')
+parser.add_argument('--var_snr_max', default=30.0, type=float,
+                    help='Soft SNR ceiling in dB of --var_loss snr')
+parser.add_argument('--var_inactive_snr_max', default=20.0, type=float,
+                    help='--var_speakers 1: ceiling in dB of a silent output\'s score')
 
 
 def reorder_inverse(est, source, lengths):
@@ -101,6 +118,10 @@ class Evaluator:
                 stoi.device_ratio(args.sample_rate)
             except ValueError as e:
                 raise SystemExit(f"--cal_stoi 1: {e}")
+        if getattr(args, 'var_speakers', 0) and (args.cal_sdr or getattr(args, 'cal_stoi', 0) or
+                                                 getattr(args, 'mixit_remix', 0)):
+            raise SystemExit("--var_speakers 1: BSS Eval and STOI are undefined against a silent source, and the "
+                             "MixIT remix pairs differently: use it without --cal_sdr, --cal_stoi and --mixit_remix")
         self.model = ConvTasNet.load_model(args.model_path)
         print(self.model)
         self.model.eval().cuda()
@@ -108,6 +129,7 @@ class Evaluator:
         self.loader = AudioDataLoader(dataset, batch_size=1, num_workers=args.num_workers)
         self.records = []
         self.stoi_records = []
+        self.var_records = []
         from separate import make_chunker
         self.chunker = make_chunker(self.model, getattr(args, 'chunk_s', 0.0), getattr(args, 'chunk_overlap_s', None),
                                     args.sample_rate)
@@ -137,12 +159,23 @@ class Evaluator:
                 raise ValueError("--mixit_remix 1 remixes to two sources per mixture, got %d" % source.size(1))
             return cal_mixit_loss(source, est.contiguous(), lengths, getattr(self.args, 'mixit_loss', 'snr'),
                                   getattr(self.args, 'mixit_snr_max', 30.0))[3]
+        if getattr(self.args, 'var_speakers', 0):
+            from pit_var_criterion import cal_loss_var
+            est = est.contiguous()
+            _, _, perm, active = cal_loss_var(source, est, lengths, mixture, getattr(self.args, 'var_loss', 'snr'),
+                                              getattr(self.args, 'var_snr_max', 30.0),
+                                              getattr(self.args, 'var_inactive_snr_max', 20.0))
+            self._var = cal_var_batch(source, est, mixture, lengths, perm, active,
+                                      getattr(self.args, 'var_count_db', -20.0))
+            return pair_by_perm(est, perm)
         _, _, est, paired = cal_loss(source, est, lengths)
         if self.args.pit_fix:
             paired = reorder_inverse(est, source, lengths)
         return paired
 
     def _score(self, mixture, lengths, source, paired):
+        if getattr(self.args, 'var_speakers', 0):
+            return [(si, None) for si in self._var[0].cpu().tolist()]
         sisnri = cal_SISNRi_batch(source, paired, mixture, lengths).cpu().tolist()
         sdri = [None] * len(sisnri)
         if self.args.cal_sdr and getattr(self.args, 'sdr_device', 0):
@@ -171,6 +204,11 @@ class Evaluator:
                     self.stoi_records.append(sv)
                     print("\tSTOI={0:.3f}".format(sv[0]))
                     print("\tESTOI={0:.3f}".format(sv[1]))
+            if getattr(self.args, 'var_speakers', 0):
+                _, silent_db, count_ok = (v.cpu().tolist() for v in self._var)
+                self.var_records.extend(zip(silent_db, count_ok))
+        if self.var_records:
+            return self._var_summary()
         n = len(self.records)
         if self.args.cal_sdr:
             print("Average SDR improvement: {0:.2f}".format(sum(r[1] for r in self.records) / n))
@@ -180,6 +218,51 @@ class Evaluator:
             for k, name in enumerate(("STOI", "ESTOI", "STOI of the mixture", "ESTOI of the mixture")):
                 print("Average {0}: {1:.3f}".format(name, sum(r[k] for r in self.stoi_records) / n))
         return mean_sisnri
+
+
+    def _var_summary(self):
+        """The averages of --var_speakers 1 (NaN: no utterance has such a source)."""
+        si = [r[0] for r in self.records if r[0] == r[0]]
+        quiet = [r[0] for r in self.var_records if r[0] == r[0]]
+        mean_sisnri = sum(si) / len(si) if si else float("nan")
+        print("Average SISNR improvement over the active sources: {0:.2f}".format(mean_sisnri))
+        print("Average level of the outputs paired with silent sources: {0:.1f} dB relative to the mixture"
+              .format(sum(quiet) / len(quiet) if quiet else float("nan")))
+        print("Utterances with the right number of outputs above {0:.0f} dB: {1:.1f} %".format(
+            getattr(self.args, 'var_count_db', -20.0),
+            100.0 * sum(1 for r in self.var_records if r[1]) / len(self.var_records)))
+        return mean_sisnri
+
+
+def pair_by_perm(est, perm):
+    """est [B, C, T], perm [B, C] (perm[b, i] = the source of output i) -> the outputs in source
+    order: index j holds the output paired with source j."""
+    inv = torch.empty_like(perm)
+    inv.scatter_(1, perm, torch.arange(perm.size(1), device=perm.device).expand_as(perm).contiguous())
+    return torch.gather(est, 1, inv.unsqueeze(-1).expand(-1, -1, est.size(-1)))
+
+
+def cal_var_batch(source, est, mixture, lengths, perm, active, count_db=-20.0, eps=1e-8):
+    """The figures of --var_speakers 1 for a padded batch (fp64, on the tensors' device): source /
+    est [B, C, T], mixture [B, T], lengths [B], perm / active [B, C] from cal_loss_var ->
+    (SI-SNRi [B] averaged over the active sources, level [B] in dB relative to the mixture averaged
+    over the outputs paired with silent sources, count_ok [B] bool: as many outputs above
+    count_db as active sources).  NaN where an utterance has no such source."""
+    B, C, T = source.shape
+    dev = source.device
+    lengths = lengths.to(dev)
+    valid = (torch.arange(T, device=dev).unsqueeze(0) < lengths.unsqueeze(1)).double()          # [B, T]
+    mask, n = valid.unsqueeze(1).expand(B, C, T), lengths.double().unsqueeze(1).expand(B, C)
+    s, e, x = source.double(), pair_by_perm(est, perm).double(), mixture.double()
+    gain = _sisnr_rows(s, e, mask, n, eps) - _sisnr_rows(s, x.unsqueeze(1).expand(B, C, T), mask, n, eps)
+    act = active.to(dev).double()
+    nan = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+    k = act.sum(1)
+    sisnri = torch.where(k > 0, (gain * act).sum(1) / k.clamp(min=1), nan)
+    level = 10 * torch.log10(((e * e * mask).sum(-1) + eps) / ((x * x * valid).sum(-1, keepdim=True) + eps))   # [B, C]
+    silent_db = torch.where(k < C, (level * (1 - act)).sum(1) / (C - k).clamp(min=1), nan)
+    count_ok = (level > count_db).sum(1) == active.to(dev).sum(1)
+    return sisnri, silent_db, count_ok
 
 
 def evaluate(args):

@@ -99,6 +99,11 @@ class Solver(object):
         self.mixit = getattr(args, 'loss', 'pit') == 'mixit'
         self.mixit_loss = getattr(args, 'mixit_loss', 'snr')
         self.mixit_snr_max = getattr(args, 'mixit_snr_max', 30.0)
+        # --loss pit_var (pit_var_criterion.py): sources that are all zero are silent
+        self.pit_var = getattr(args, 'loss', 'pit') == 'pit_var'
+        self.var_loss = getattr(args, 'var_loss', 'snr')
+        self.var_snr_max = getattr(args, 'var_snr_max', 30.0)
+        self.var_inactive_snr_max = getattr(args, 'var_inactive_snr_max', 20.0)
         self.schedule = PlateauSchedule(bool(args.half_lr), bool(args.early_stop))
         self.tr_loss = torch.zeros(self.epochs)
         self.cv_loss = torch.zeros(self.epochs)
@@ -201,9 +206,16 @@ class Solver(object):
         return tuple(t.to(dev, non_blocking=True) for t in batch)
 
     def _loss(self, model, mixture, lengths, source, cross_valid):
-        """The loss of one batch: PIT against the sources, or, with --loss mixit, MixIT."""
+        """The loss of one batch: PIT against the sources, with --loss mixit MixIT, with
+        --loss pit_var PIT with silent sources."""
         # with mixture consistency on (DESIGN.md §28) the model projects within each length
         mc = getattr(_inner(model), 'mixture_consistency', 'none') != 'none'
+        if self.pit_var:
+            # the batch's input mixture is the silent outputs' yardstick: additive noise counts
+            from pit_var_criterion import cal_loss_var
+            est = model(mixture, lengths) if mc else model(mixture)
+            return cal_loss_var(source, est, lengths, mixture, self.var_loss, self.var_snr_max,
+                                self.var_inactive_snr_max)[0]
         if not self.mixit:
             return cal_loss(source, model(mixture, lengths) if mc else model(mixture), lengths)[0]
         from mixit_criterion import cal_mixit_loss, mom_pairs

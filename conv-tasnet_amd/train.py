@@ -35,7 +35,15 @@ Differences, each deliberate:
   outputs to the two sources of each validation mixture;
 * ``--mixture_consistency uniform|power`` (default ``none``: nothing changes) puts the
   mixture-consistency projection on the model's outputs (mixture_consistency.py, DESIGN.md
-  §28), with either loss; the mode is written into the package.
+  §28), with either loss; the mode is written into the package;
+* ``--loss pit_var`` (pit_var_criterion.py) trains one model with ``--C`` outputs
+  (2 to 8) on mixtures of 1 to C speakers: a source that is all zero is silent, its output is
+  scored by how far it lies below the input mixture, and the permutation is searched over
+  active and silent sources together (``--var_loss snr|si_snr``, ``--var_snr_max``,
+  ``--var_inactive_snr_max``).  ``--dm_min_speakers K`` (default 0: always C) lets the dynamic
+  mixer draw how many of a row's slots speak, K to C; it needs ``--loss pit_var`` or ``mixit``,
+  because the plain PIT loss scores a silent source as noise.  Cross validation uses the same
+  loss on the fixed set, whose silent sources are all-zero files.
 """
 import argparse
 import os
@@ -162,10 +170,11 @@ parser.add_argument('--dm_snr_db', default=[-5.0, 5.0], type=float, nargs=2, met
                     help='Range of the uniform draw of the clean mixture to noise ratio (dB)')
 
 # MixIT (mixit_criterion.py); pit: the reference's loss on isolated sources
-parser.add_argument('--loss', default='pit', type=str, choices=['pit', 'mixit'],
+parser.add_argument('--loss', default='pit', type=str, choices=['pit', 'mixit', 'pit_var'],
                     help='pit: PIT SI-SNR against the sources.  mixit: mixture-invariant training, every two '
                          'utterances of a batch are added into one mixture of mixtures and --C is the number of '
-                         'model outputs; the sources are not used')
+                         'model outputs; the sources are not used.  pit_var: PIT in which an all-zero source is '
+                         'silent and its output is pushed below the mixture (1 to --C speakers per mixture)')
 parser.add_argument('--mixit_loss', default='snr', type=str, choices=['snr', 'si_snr'],
                     help='MixIT score: snr (thresholded at --mixit_snr_max) or si_snr')
 parser.add_argument('--mixit_snr_max', default=30.0, type=float,
@@ -173,6 +182,16 @@ parser.add_argument('--mixit_snr_max', default=30.0, type=float,
 parser.add_argument('--mixit_speakers', default=2, type=int,
                     help='Speakers the dynamic mixer draws per single mixture under --loss mixit')
 
+# PIT with silent sources (pit_var_criterion.py)
+parser.add_argument('--var_loss', default='snr', type=str, choices=['snr', 'si_snr'],
+                    help='pit_var score of an active source: snr (thresholded at --var_snr_max) or si_snr')
+parser.add_argument('--var_snr_max', default=30.0, type=float,
+                    help='pit_var soft SNR ceiling of an active source in dB (snr only)')
+parser.add_argument('--var_inactive_snr_max', default=20.0, type=float,
+                    help='pit_var: an output paired with a silent source is pushed this many dB below the mixture')
+parser.add_argument('--dm_min_speakers', default=0, type=int,
+                    help='Dynamic mixing: every row keeps a drawn number of its speakers, from this many to all '
+                         '(0: always all; needs --loss pit_var or mixit)')
 
 # mixture consistency (mixture_consistency.py); none: the reference's model
 parser.add_argument('--mixture_consistency', default='none', type=str, choices=['none', 'uniform', 'power'],
@@ -203,6 +222,28 @@ def check_mixit(args):
         raise ValueError(f"--mixit_snr_max {args.mixit_snr_max}: a finite value in dB")
     if args.mixit_speakers < 1:
         raise ValueError(f"--mixit_speakers {args.mixit_speakers}: at least 1")
+
+
+def check_var(args):
+    """--loss pit_var and --dm_min_speakers: exits with the reason when they cannot work."""
+    import math
+    loss, k = getattr(args, 'loss', 'pit'), getattr(args, 'dm_min_speakers', 0)
+    if loss == 'pit_var':
+        if not 2 <= args.C <= 8:
+            raise SystemExit(f"--loss pit_var: --C {args.C} is the number of model outputs, 2 to 8")
+        if not (math.isfinite(args.var_snr_max) and math.isfinite(args.var_inactive_snr_max)):
+            raise SystemExit("--var_snr_max and --var_inactive_snr_max: finite values in dB")
+    if k == 0:
+        return
+    slots = args.mixit_speakers if loss == 'mixit' else args.C
+    if not 1 <= k <= slots:
+        raise SystemExit(f"--dm_min_speakers {k}: 1 to the {slots} speakers the mixer draws "
+                         f"({'--mixit_speakers' if loss == 'mixit' else '--C'}), or 0 for all of them")
+    if not args.dynamic_mix:
+        raise SystemExit("--dm_min_speakers thins the dynamically mixed batches: it needs --dynamic_mix 1")
+    if k < slots and loss == 'pit':
+        raise SystemExit(f"--dm_min_speakers {k} with --C {args.C} leaves silent sources in the batch, and --loss pit "
+                         f"scores a silent source as noise (SI-SNR against zero): use --loss pit_var")
 
 
 def minibatch_rows(mb):
@@ -263,7 +304,8 @@ def dynamic_mix_loader(args, static_loader, rank, world):
     mixer = DynamicMixer(corpus, args.batch_size, speakers, int(args.segment * args.sample_rate), seed=args.dm_seed,
                          level_mode=args.dm_level_mode, level_db=tuple(args.dm_level_db), peak=args.dm_peak,
                          rank=rank, world=world, speeds=args.dm_speeds, rirs=rirs, rir_prob=args.dm_rir_prob,
-                         noise=noise, snr_db=tuple(args.dm_snr_db))
+                         noise=noise, snr_db=tuple(args.dm_snr_db),
+                         min_speakers=getattr(args, 'dm_min_speakers', 0) or None)
     steps = args.dm_steps if args.dm_steps > 0 else len(static_loader)
     if rank == 0:
         print("Dynamic mixing: {} utterances ({:.1f} MB on the device), {} steps per epoch".format(
@@ -296,6 +338,7 @@ class FlatDP(Single):
 
 def main(args):
     check_mixit(args)
+    check_var(args)
     check_mixture_consistency(args)
     check_dm_speeds(args)
     check_dm_aug(args)

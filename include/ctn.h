@@ -263,6 +263,48 @@ int ctn_mixit_backward(const ctn_mixit_desc* d, const float* mixtures, const flo
                        float* g_est /*[M][C][T]*/, void* stream);
 
 /* -------------------------------------------------------------------------
+ * PIT with silent sources (Wisdom et al. 2021, "What's all the FUSS about free universal sound
+ * separation data?", section 4): a model with C outputs is scored against 0 ... C speaking
+ * references.  An active reference is scored by (SI-)SNR, a silent one by how far its output
+ * lies below the mixture, and the permutation is searched over both kinds together.  Added
+ * within ABI v13 without a version bump (nothing existing changed): callers probe for the
+ * symbol.  No reference counterpart; DESIGN.md §29 has the full definition.
+ *
+ * source, est [M][C][T], mixture [M][T] (nullable) fp32 contiguous, 2 <= C <= 8, lengths [M]
+ * (>= 1; values above T count as T).  All sums run over t < n = min(lengths[m], T) in fp64;
+ * nothing is masked in place and est is never written.  EPS = 1e-8, tau = 10^(-snr_max / 10),
+ * tau0 = 10^(-inactive_snr_max / 10).
+ *   x = mixture, or without one x[t] = sum_j s_j[t] in ascending j;  X = sum x^2.
+ *   Reference j is active iff S_j = sum s_j^2 > 0: inactive iff every sample inside the length
+ *   is +-0 (no threshold).  active [M][C] receives 1 / 0.
+ *   Output i against an active j:
+ *     mode CTN_PITVAR_SNR:    10 log10((S_j + EPS) / (R_ij + tau S_j + EPS)), R_ij = sum (s_j - e_i)^2;
+ *     mode CTN_PITVAR_SI_SNR: the zero-mean SI-SNR of ctn_pit_forward, both means over t < n.
+ *   Output i against an inactive j: 10 log10((X + EPS) / (E_i + tau0 X + EPS)), E_i = sum e_i^2.
+ * perm [M][C] (perm[m][i] = the reference of output i) maximises sum_i score[i][perm[i]] over
+ * all C! permutations: the first maximum in lexicographic (itertools.permutations) order, which
+ * decides the k! exact ties of k silent references.  max_snr[m] = that sum / C;
+ * loss = -mean_m max_snr[m].  All statistics and the search are fp64 in a fixed order without
+ * atomics: two calls on the same inputs give the same bits.  coef [M][C][4] (al, be, off, j) is
+ * saved for the backward,
+ *   g_est[m][i][t] = (g_max_snr[m] - g_loss / M) (al s_j[t] + be e_i[t] + off),
+ * for t < n and exactly 0 beyond (g_max_snr nullable: zeros); al = 0 for an inactive j.
+ * An unsupported descriptor (C < 2, C > 8, unknown mode, non-finite snr_max or
+ * inactive_snr_max) has 0 workspace bytes; the entries check descriptor, pointers and workspace
+ * before anything is launched, and neither synchronises (both can be captured into a graph).
+ * ------------------------------------------------------------------------- */
+enum { CTN_PITVAR_SNR = 0, CTN_PITVAR_SI_SNR = 1 };
+typedef struct { int32_t M, C, T, mode; float snr_max, inactive_snr_max; } ctn_pitvar_desc;
+size_t ctn_pitvar_workspace_bytes(const ctn_pitvar_desc* d);
+int ctn_pitvar_forward(const ctn_pitvar_desc* d, const float* source, const float* est, const float* mixture,
+                       const int64_t* lengths, float* loss, float* max_snr /*[M]*/, int64_t* perm /*[M][C]*/,
+                       uint8_t* active /*[M][C]*/, float* coef /*[M][C][4]*/, void* ws, size_t ws_bytes,
+                       void* stream);
+int ctn_pitvar_backward(const ctn_pitvar_desc* d, const float* source, const float* est, const int64_t* lengths,
+                        const float* coef, const float* g_loss, const float* g_max_snr,
+                        float* g_est /*[M][C][T]*/, void* stream);
+
+/* -------------------------------------------------------------------------
  * Mixture-consistency projection (Wisdom et al. 2019, "Differentiable consistency
  * constraints for improved deep speech enhancement"): the residual of the model's C outputs
  * against the input mixture is spread over the outputs, so that they add up to the mixture.
@@ -430,6 +472,21 @@ int ctn_dmix_draw(const ctn_dmix_desc* d, const int64_t* off /*[n_utts+1]*/, con
 int ctn_dmix_mix(const ctn_dmix_desc* d, const void* pool, const int64_t* off /*[n_utts+1]*/,
                  const ctn_dmix_entry* plan /*[M][C]*/, float* gains /*[M][C]*/, float* sources /*[M][C][T]*/,
                  float* mixture /*[M][T]*/, int32_t* status /*[M]*/, void* ws, size_t ws_bytes, void* stream);
+
+/* Dynamic mixing with a drawn number of speakers: after any of the draw entries, row m keeps
+ * n_m = min_speakers + ((r0 (C - min_speakers + 1)) >> 32) of its C slots, r0 = word 0 of
+ * philox4x32_10((g_lo, g_hi, 48, 0), seed) for the row's global sample g (a counter word 2 next
+ * to the RIR draws' 16 + c and the noise draw's 32: no existing draw moves).  Slots c >= n_m get
+ * level_db = -inf, every other bit of the plan stays; count[m] = n_m.  The mix entries need no
+ * change: exp10(-inf / 20) is exactly 0 in both level modes, so a thinned slot drops out of the
+ * mixture, the peak guard and the noise power, and its written source is +-0 everywhere.
+ * g = (first_sample_dev ? *first_sample_dev - drawn_advance : first_sample) + m: pass the draw's
+ * `advance` as drawn_advance when the draw moved the device counter.  1 <= min_speakers <= C
+ * (CTN_ERR_ARG beyond); min_speakers = C keeps every slot.  Added within ABI v13 without a
+ * version bump (nothing existing changed): callers probe for the symbol.  DESIGN.md §29. */
+int ctn_dmix_thin(const ctn_dmix_desc* d, int32_t min_speakers, int64_t first_sample,
+                  const int64_t* first_sample_dev, int64_t drawn_advance, ctn_dmix_entry* plan /*[M][C]*/,
+                  int32_t* count /*[M]*/, void* stream);
 
 /* -------------------------------------------------------------------------
  * Dynamic mixing with speed perturbation: every source is resampled by a polyphase FIR
